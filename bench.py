@@ -3,7 +3,9 @@
 16 frames x 224^2 + 128 tokens per window, B=64 windows per GPU, bf16, fused clip+AdamW) on 1..8
 MI355X, one process per GPU (torchrun), RCCL all-reduce overlapped with the backward.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times `--steps` steps, writes the last timed step's
+outputs with `--dump-outputs DIR`, and prints the line (metric, value, ms_per_step, config, host diagnostics and the
+arithmetic `roofline_step`). `--full` adds what takes runs or checks of its own:
 - `roofline`: the dominant kernel (igemm_fast_kernel, the bf16 conv/linear GEMM engine), timed live with
   HIP events on the launch stream during one extra instrumented step after the timed region
   (vcg_timing_*). Each launch records its algorithmic FLOPs (2*M*N*K) and bytes (operands read once, a
@@ -13,6 +15,8 @@ Prints ONE JSON line (rank 0).
   launch from the committed PMC pass (profiles/traffic_*.json), if any.
 - `roofline_step`: the whole step priced against HBM with SURVEY Appendix A's fused-minimum bytes.
 - `cpu_baseline`: the CPU oracle (oracle/, test infrastructure) on a bounded sample on this host.
+- the path / GEMM census of the last warm-up step against the instrumented step, and at world > 1 the
+  cross-rank parameter check and the gradient-exchange figures (`ddp_evidence`).
 """
 import argparse
 import json
@@ -182,6 +186,35 @@ def cpu_baseline(T, HW, L, threads, mode="train", B=None, reps=None, bn="running
                                "threads; 64+ ran slower)"}
 
 
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20   # all files of one dump together
+DUMP_SAMPLE = 1 << 20         # elements kept of the flat parameter / gradient buffers
+
+
+def seeded_sample(t, n):
+    """t flattened, or n of its elements at fixed (seeded, sorted) positions when it has more."""
+    import torch
+    t = t.detach().reshape(-1)
+    if t.numel() <= n:
+        return t
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every tensor of `arrays` as outdir/<name>.npy in float32, its own shape while the dump stays
+    within DUMP_LIMIT_BYTES in all, otherwise a seeded sample of its elements."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // (4 * max(len(arrays), 1))  # elements per file, headers aside
+    for name, t in arrays.items():
+        if t.numel() > share:
+            t = seeded_sample(t, share)
+        np.save(os.path.join(outdir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 # ----------------------------------------------------------------------------- config 5
 def long_video_bench(args):
     """Config 5: one 1 h synthetic video (u8 frames resident in HBM), stride-1 s windows, frame gather +
@@ -224,6 +257,8 @@ def long_video_bench(args):
     scores, labels = lv.score_windows(model, frames, idx, ids, mask, B, streams=K, groups=G)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": scores, "labels": labels})
     lab = labels.cpu().tolist()
     m = lv.boundary_metrics(lab, timestamps, F, T, args.stride)
     n = len(win)
@@ -379,6 +414,53 @@ def launch_check(args, world, rank):
         dist.destroy_process_group()
 
 
+# ----------------------------------------------------------------------------- --full
+def instrumented_step(args, model, step, dom_id, peak_tf, timed_census, timed_gemms):
+    """--full: one extra (untimed) step with every fast-GEMM launch bracketed by HIP events, checked against the
+    census of the last warm-up step. Returns the dominant kernel's totals, the per-category roofline records, the
+    wide engine's launch count and the two census summaries."""
+    import torch
+    from vcg_hip import ops
+    from vcg_hip.trunk import ResNetTrunk
+    # BERT runs on the trunk's stream for this step, so a launch's duration is the kernel's own (not shared with a
+    # concurrent kernel)
+    sides = (model.overlap_streams, ResNetTrunk.wgrad_stream, ResNetTrunk.ds_stream)
+    # (and the weight gradients / downsample convs / weight re-layout on the trunk's stream)
+    model.overlap_streams = ResNetTrunk.wgrad_stream = ResNetTrunk.ds_stream = False
+    ops.timing_enable(True)
+    census = gemm_census = None
+    if not args.no_roofline_step:
+        ResNetTrunk.census = [] if timed_census is not None else None
+        ops.gemm_census_enable(timed_gemms is not None)
+        step()
+        inst_census, ResNetTrunk.census = ResNetTrunk.census, None
+        if timed_gemms is not None:
+            inst_gemms = ops.gemm_census()
+            ops.gemm_census_enable(False)
+            # every GEMM of the instrumented step on the kernel the timed steps used (no silent fallback between them)
+            assert inst_gemms == timed_gemms, ("instrumented step ran other GEMM kernels than the timed steps",
+                                               sorted(set(inst_gemms.items()) ^ set(timed_gemms.items()))[:8])
+            gemm_census = gemm_census_summary(timed_gemms)
+        if timed_census is not None:
+            # the one-stream instrumented step must run the timed step's kernels (bn3 folds, y3 drops, GEMM passes)
+            assert inst_census == timed_census, ("instrumented step ran another per-block path than the timed steps",
+                                                 timed_census, inst_census)
+            census = {"blocks_fwd": sum(e[0] == "fwd" for e in timed_census),
+                      "blocks_bwd": sum(e[0] == "bwd" for e in timed_census),
+                      "bn3_fold_bwd": sum(e[0] == "bwd" and e[3]["fold_dgrad"] for e in timed_census),
+                      "y3_drop": sum(e[0] == "fwd" and e[3]["y3_drop"] for e in timed_census),
+                      "identical_to_timed_step": True}
+    torch.cuda.synchronize()
+    k_ms, k_n, k_fl = ops.timing_query(dom_id)
+    rl = {kid: ops.timing_roofline(kid, peak_tf, HBM_PEAK_GBS) for kid in (dom_id, ops.TIMING_WGRAD,
+                                                                           ops.TIMING_WIDE_GEMM)}
+    wide_n = ops.timing_query(ops.TIMING_WIDE_GEMM)[1]
+    ops.timing_enable(False)
+    model.overlap_streams, ResNetTrunk.wgrad_stream, ResNetTrunk.ds_stream = sides
+    kern = {"ms": k_ms, "launches": k_n, "flops": k_fl}
+    return kern, rl, wide_n, census, gemm_census
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -413,11 +495,17 @@ def main():
     ap.add_argument("--full-text", action="store_true",
                     help="synthetic subtitles fill all --tokens positions (default: n_valid uniform in [L/2, L], "
                          "vcg_hip.synth.clip_batch): the BERT work without any padded rows to drop")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the census of the last warm-up step, one instrumented step (the "
+                         "dominant-kernel roofline), the CPU baseline and, at world > 1, the DDP evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         "the inputs are seeded, so two builds can be compared output for output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-roofline-step", action="store_true",
-                    help="skip the instrumented step after the timed region (profiling runs: the trace then ends with "
-                         "the timed steps); the line then has no dominant-kernel roofline")
+                    help="with --full: skip the instrumented step after the timed region (profiling runs: the trace "
+                         "then ends with the timed steps); the line then has no dominant-kernel roofline")
     ap.add_argument("--one-stream", action="store_true",
                     help="every kernel on one HIP stream (BERT, the trunk's weight gradients and downsample branch "
                          "inline): the one-stream rocprof profiles, whose per-kernel durations are unshared")
@@ -427,6 +515,10 @@ def main():
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 16 if (args.bn == "batch" and args.mode != "train") else 64
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_roofline_step = True
 
     if args.bn_groups > 1 and (args.bn != "batch" or args.mode == "train" or args.scoring_streams > 1):
         raise SystemExit("bench.py: --bn-groups applies to batch-statistics scoring (--bn batch, fwd / long_video) "
@@ -518,12 +610,15 @@ def main():
     pool = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(device=dev) for _ in range(K - 1)]
     comm_events = None  # [(backward done, finish joined)] per timed step (world > 1)
     prepared = []
+    keep = {} if (args.dump_outputs and rank == 0) else None  # --dump-outputs: what the latest step returned
 
     def step():
         if args.mode == "fwd":
             with torch.no_grad():
                 if K == 1:
-                    model(frames, ids, mask)
+                    res = model(frames, ids, mask)
+                    if keep is not None:
+                        keep.update(logits=res[0], prob=res[1])
                     return
                 main = pool[0]
                 if not prepared:  # the first forward prepares the weights on the main stream
@@ -534,7 +629,9 @@ def main():
                     if k == 0 and not prepared:
                         continue
                     with torch.cuda.stream(pool[k]):
-                        model(f_, i_, m_)
+                        res = model(f_, i_, m_)
+                    if keep is not None:
+                        keep[f"logits_{k}"], keep[f"prob_{k}"] = res[0], res[1]
                 prepared.append(True)
                 for s_ in pool[1:]:
                     main.wait_stream(s_)
@@ -545,6 +642,8 @@ def main():
         logits, prob = model(frames, ids, mask)
         loss = cross_entropy(logits, labels)
         loss.backward()
+        if keep is not None:
+            keep.update(logits=logits, prob=prob, loss=loss)
         if comm_events is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -562,7 +661,7 @@ def main():
     # vcg_gemm_census) of the same step: the instrumented step below must match it launch for launch
     timed_census = timed_gemms = None
     for i in range(args.warmup):
-        last = i == args.warmup - 1
+        last = args.full and i == args.warmup - 1
         if last and args.mode == "train":
             ResNetTrunk.census = []
         if last:
@@ -607,52 +706,28 @@ def main():
     torch.cuda.synchronize()
     ms = ev0.elapsed_time(ev1) / args.steps
     ms = max(ms, wall * 1000.0 / args.steps)
-    # one extra (untimed) step with every fast-GEMM launch bracketed by HIP events; BERT runs on the trunk's
-    # stream for this step, so a launch's duration is the kernel's own (not shared with a concurrent kernel)
-    sides = (model.overlap_streams, ResNetTrunk.wgrad_stream, ResNetTrunk.ds_stream)
-    # (and the weight gradients / downsample convs / weight re-layout on the trunk's stream)
-    model.overlap_streams = ResNetTrunk.wgrad_stream = ResNetTrunk.ds_stream = False
-    ops.timing_enable(True)
-    census = gemm_census = None
-    if not args.no_roofline_step:
-        ResNetTrunk.census = [] if timed_census is not None else None
-        ops.gemm_census_enable(timed_gemms is not None)
-        step()
-        inst_census, ResNetTrunk.census = ResNetTrunk.census, None
-        if timed_gemms is not None:
-            inst_gemms = ops.gemm_census()
-            ops.gemm_census_enable(False)
-            # every GEMM of the instrumented step on the kernel the timed steps used (no silent fallback between them)
-            assert inst_gemms == timed_gemms, ("instrumented step ran other GEMM kernels than the timed steps",
-                                               sorted(set(inst_gemms.items()) ^ set(timed_gemms.items()))[:8])
-            gemm_census = gemm_census_summary(timed_gemms)
-        if timed_census is not None:
-            # the one-stream instrumented step must run the timed step's kernels (bn3 folds, y3 drops, GEMM passes)
-            assert inst_census == timed_census, ("instrumented step ran another per-block path than the timed steps",
-                                                 timed_census, inst_census)
-            census = {"blocks_fwd": sum(e[0] == "fwd" for e in timed_census),
-                      "blocks_bwd": sum(e[0] == "bwd" for e in timed_census),
-                      "bn3_fold_bwd": sum(e[0] == "bwd" and e[3]["fold_dgrad"] for e in timed_census),
-                      "y3_drop": sum(e[0] == "fwd" and e[3]["y3_drop"] for e in timed_census),
-                      "identical_to_timed_step": True}
-    torch.cuda.synchronize()
+    if keep:
+        # the last timed step as its caller sees it: the forward's results and, in a train step, the gradients it
+        # left and the parameters it updated (a seeded sample of the flat buffers)
+        if args.mode == "train":
+            keep.update(grads_sample=seeded_sample(flat.grad, DUMP_SAMPLE),
+                        params_sample=seeded_sample(flat.data, DUMP_SAMPLE))
+        dump_outputs(args.dump_outputs, keep)
     # the dominant kernel: the bf16 fast engine, or the generic engine (exact fp32 MFMA) in the parity precision
     dom_id, dom_name = ((ops.TIMING_FAST_GEMM, "igemm_fast_kernel") if args.precision == "bf16"
                         else (ops.TIMING_GENERIC_GEMM, "igemm_kernel"))
-    k_ms, k_n, k_fl = ops.timing_query(dom_id)
     peak_tf = MFMA_PEAK_TFLOPS[args.precision]
-    rl = {kid: ops.timing_roofline(kid, peak_tf, HBM_PEAK_GBS) for kid in (dom_id, ops.TIMING_WGRAD,
-                                                                           ops.TIMING_WIDE_GEMM)}
-    wide_n = ops.timing_query(ops.TIMING_WIDE_GEMM)[1]
-    ops.timing_enable(False)
-    model.overlap_streams, ResNetTrunk.wgrad_stream, ResNetTrunk.ds_stream = sides
-    kern = {"ms": k_ms, "launches": k_n, "flops": k_fl}
+    census = gemm_census = None
+    kern, rl, wide_n = {"ms": 0.0, "launches": 0, "flops": 0.0}, {}, 0
+    if args.full:
+        kern, rl, wide_n, census, gemm_census = instrumented_step(args, model, step, dom_id, peak_tf, timed_census,
+                                                                  timed_gemms)
     ddp = {}
     if world > 1:
         t = torch.tensor([ms], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ms = float(t.item())
-        if args.mode == "train":
+        if args.full and args.mode == "train":
             ddp = ddp_evidence(reducer, flat, exposed, "libvcg_hip RCCL C ABI" if comm is not None else
                                "torch.distributed")
 

@@ -51,3 +51,25 @@ def test_bench_world_mismatch_fails():
 def test_bench_long_video_rejects_multi_gpu():
     p = _run(["--gpus", "2", "--mode", "long_video"])
     assert p.returncode != 0 and "one-GPU" in (p.stderr + p.stdout)
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """--dump-outputs' writer: every array as <name>.npy in float32, a small one in its own shape, one too large for
+    the 64 MB a dump may take as a sample at fixed (seeded) positions, the same from call to call."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    big = torch.arange(20_000_000, dtype=torch.float32)  # 80 MB: over the limit by itself
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"logits": small, "loss": small.sum(), "big": big})
+    files = {f.stem: np.load(f, allow_pickle=False) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(files) == {"logits", "loss", "big"} and all(a.dtype == np.float32 for a in files.values())
+    assert files["logits"].shape == (2, 3) and files["loss"].shape == () and files["loss"] == 15.0
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 64 << 20
+    s = files["big"]
+    assert 1 << 20 < s.size < big.numel() and (np.diff(s) >= 0).all() and s[-1] > 0.99 * big.numel()
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    kept = bench.seeded_sample(big, 1000)
+    assert kept.numel() == 1000 and torch.equal(kept, bench.seeded_sample(big, 1000))
+    assert torch.equal(bench.seeded_sample(small, 1000), small.reshape(-1))

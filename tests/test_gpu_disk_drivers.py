@@ -124,7 +124,7 @@ def test_bench_gpus2_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["VCG_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup",
-                          "1", "--batch", "2", "--frames", "4", "--res", "112", "--tokens", "32"],
+                          "1", "--batch", "2", "--frames", "4", "--res", "112", "--tokens", "32", "--full"],
                          capture_output=True, text=True, timeout=400, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

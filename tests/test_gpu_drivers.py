@@ -70,7 +70,7 @@ def test_bench_script_small():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--batch",
-                          "2", "--frames", "4", "--res", "112", "--tokens", "32", "--no-cpu-baseline"],
+                          "2", "--frames", "4", "--res", "112", "--tokens", "32", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

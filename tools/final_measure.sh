@@ -4,9 +4,10 @@
 set -o pipefail
 TAG=${1:-fin}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
-timeout -k 10 600 python bench.py > gpurun_out/${TAG}_train.json 2> gpurun_out/${TAG}_train.err || { echo "bench failed"; tail -20 gpurun_out/${TAG}_train.err; exit 1; }
-tail -1 gpurun_out/${TAG}_train.json | cut -c1-300
-bash tools/traffic.sh ${TAG}_tr > gpurun_out/${TAG}_tr.txt 2>&1 || { echo "traffic failed"; exit 2; }
-bash tools/mfma.sh ${TAG}_mf > gpurun_out/${TAG}_mf.txt 2>&1 || { echo "mfma failed"; exit 3; }
+OUT=${VCG_OUT:-bench_out}  # where logs and result lines go
+mkdir -p "$OUT"
+timeout -k 10 600 python bench.py --full > $OUT/${TAG}_train.json 2> $OUT/${TAG}_train.err || { echo "bench failed"; tail -20 $OUT/${TAG}_train.err; exit 1; }
+tail -1 $OUT/${TAG}_train.json | cut -c1-300
+bash tools/traffic.sh ${TAG}_tr > $OUT/${TAG}_tr.txt 2>&1 || { echo "traffic failed"; exit 2; }
+bash tools/mfma.sh ${TAG}_mf > $OUT/${TAG}_mf.txt 2>&1 || { echo "mfma failed"; exit 3; }
 bash tools/gpu_measure.sh ${TAG}_m

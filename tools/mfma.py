@@ -1,5 +1,5 @@
 """Reduce one rocprofv3 --pmc pass (SQ_VALU_MFMA_BUSY_CYCLES, SQ_BUSY_CYCLES, GRBM_GUI_ACTIVE) of
-`bench.py --steps 1 --warmup 1` to the matrix-core utilisation of each kernel -> profiles/mfma_<mode>_bf16_b64.json.
+`bench.py --full --steps 1 --warmup 1` to the matrix-core utilisation of each kernel -> profiles/mfma_<mode>_bf16_b64.json.
 
 mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs): the share of SIMD-cycles in
 which the matrix pipe was busy while the kernel ran (MI355X_MICROARCH.md: GRBM_GUI_ACTIVE is summed over the 8
@@ -37,7 +37,7 @@ def main():
     per, ndisp = load(sys.argv[1])
     steps, mode = float(sys.argv[2]), sys.argv[3]
     out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE (one pass), "
-                     f"bench.py --mode {mode} --steps 1 --warmup 1 ({int(steps)} steps incl. the instrumented one)",
+                     f"bench.py --full --mode {mode} --steps 1 --warmup 1 ({int(steps)} steps incl. the instrumented one)",
            "formula": "mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs)"}
     tot_busy = tot_cyc = 0.0
     kern = {}

@@ -7,8 +7,9 @@ set -o pipefail
 TAG=${1:-mfma}
 MODE=${2:-train}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${VCG_OUT:-bench_out}  # where logs and result lines go
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 CTRS="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-timeout -k 10 600 rocprofv3 --pmc $CTRS --output-format csv -d gpurun_out/${TAG}_pmc -o run -- python bench.py --mode $MODE --steps 1 --warmup 1 --no-cpu-baseline > gpurun_out/${TAG}_pmc.log 2>&1 || { echo "pmc pass failed"; tail -20 gpurun_out/${TAG}_pmc.log; exit 1; }
-python tools/mfma.py gpurun_out/${TAG}_pmc 3 $MODE
+timeout -k 10 600 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/${TAG}_pmc -o run -- python bench.py --full --mode $MODE --steps 1 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_pmc.log 2>&1 || { echo "pmc pass failed"; tail -20 $OUT/${TAG}_pmc.log; exit 1; }
+python tools/mfma.py $OUT/${TAG}_pmc 3 $MODE

@@ -1,4 +1,4 @@
-"""Reduce two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --steps 1 --warmup 1`
+"""Reduce two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --full --steps 1 --warmup 1`
 to HBM bytes per step and per igemm_fast_kernel launch -> profiles/traffic_train_bf16_b64.json.
 FETCH_SIZE / WRITE_SIZE are reported in KiB (x1024). gfx950 correction (MI355X_MICROARCH.md § HBM):
 FETCH_SIZE counts half the bytes of 16-B/lane streaming reads -> x2; WRITE_SIZE is exact for 16-B/lane
@@ -38,7 +38,7 @@ def main():
     g_f, g_w = fetch.get("igemm_fast_kernel", [0, 0]), write.get("igemm_fast_kernel", [0, 0])
     launches = max(g_f[1], 1)
     out = {
-        "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --mode {mode} --steps 1 --warmup 1 "
+        "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --full --mode {mode} --steps 1 --warmup 1 "
                   "(3 steps incl. the instrumented one); FETCH x2 (gfx950 correction)",
         "hbm_bytes_per_step": tot / steps,
         "igemm_fast_kernel": {"hbm_bytes_per_launch": (2 * g_f[0] + g_w[0]) / launches,

@@ -681,14 +681,15 @@ class ResNetTrunk:
                                          b3.bn.weight, sums3[0], sums3[1], M, a2s,
                                          blk.conv3.weight.grad.view(C3, planes))
                 return True
-            return self._async(wfn, a2, g, sums3, a2s, Pg0, G0)
+            # (b3.vec: bn3's mean / invstd, owned by the block's record, which is dropped before the side stream ran)
+            return self._async(wfn, a2, g, sums3, a2s, Pg0, G0, b3.vec)
 
         def wfn():
             cs = torch.empty(planes, dtype=torch.float32, device=a2.device)
             ops.colsum(a2.view(M, planes), planes, M, planes, cs, accumulate=False)
             return ops.conv_wgrad_bnfold(a2, g, y3, b3.mean, b3.invstd, b3.bn.weight, sums3[0], sums3[1], M, cs,
                                          blk.conv3.weight.grad, N, H2, W2, planes, C3)
-        return self._async(wfn, a2, g, y3, sums3)
+        return self._async(wfn, a2, g, y3, sums3, b3.vec)
 
     def _dgrad_bn_fold(self, conv, g, y3, b3, sums3, N, H, W, y, st, C, C3, a2=None, a2sum=None):
         """_dgrad_bn of conv3 with bn3's backward folded in: one GEMM over [g | y3] against [A w | B w] (or, with
@@ -744,7 +745,7 @@ class ResNetTrunk:
                     def dyd_fn():
                         return self._bn_apply_bwd(g, r["yd"], bd, C3, sumsd)
                     if self._ws is not None and self.ds_stream:
-                        dyd = self._async(dyd_fn, g, r["yd"], *sumsd)
+                        dyd = self._async(dyd_fn, g, r["yd"], bd.vec, *sumsd)
                     else:
                         dyd = dyd_fn()
             elif ResNetTrunk.dual_bn_bwd and ds and b3.mode != "running" and bd.mode != "running":  # g read once

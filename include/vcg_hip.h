@@ -271,17 +271,23 @@ VCG_API long long vcg_colsum_ws_bytes(int rows, int N);
 VCG_API int vcg_colsum(int dtype, const void* x, long long ld, int rows, int N, float* out, int accumulate, float* ws, long long ws_bytes, hipStream_t s);
 VCG_API int vcg_attn_softmax_fwd(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh, int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_attn_softmax_bwd(int dtype, const void* dPd, const void* P, void* dS, int Z, int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
-/* fused self-attention (bert_attn.hip), bf16, L <= 128, head dim 64: ctx = dropout(softmax(scale QK^T + mask)) V
-   per (sequence, head) in one workgroup, nothing L x L in HBM; stats [B*nh][128] float2 (row max, 1 / row sum)
-   for the backward, which recomputes P and writes dQ | dK | dV into dqkv [B*L][3*H] (its ctx argument may be
-   NULL: the row term rowsum(dP o P) comes from the fp32 products, not from the forward's output). Same semantics and dropout
+/* fused self-attention, bf16, L <= 512, head dim 64: ctx = dropout(softmax(scale QK^T + mask)) V, nothing L x L in
+   HBM. L <= 128 (bert_attn.hip): one workgroup per (sequence, head); 128 < L <= 512 (bert_attn_long.hip): 128 x 128
+   tiles with an online softmax, the backward as two kernels (D and dQ per query tile, dK and dV per key tile, no
+   atomics); L > 512: VCG_ERR_UNSUPPORTED. stats: vcg_bert_attn_stats_bytes(B, nh, L) bytes the forward fills for the
+   backward -- float2 (row max, 1 / row sum) per query ([B*nh][128] at L <= 128; above it over L rounded up to 128,
+   followed by the float vector D = rowsum(dP o P) that the backward writes there itself, which is why the backward's
+   stats is not read-only at L > 128). The backward recomputes P and writes dQ | dK | dV into dqkv [B*L][3*H] (its ctx
+   argument may be NULL: D comes from the fp32 products, not from the forward's output). Same semantics and dropout
    mask as vcg_attn_softmax_fwd/bwd + the batched GEMMs (HF BertSelfAttention, bert_hugface.py:20). */
+VCG_API long long vcg_bert_attn_stats_bytes(int B, int nh, int L);
 VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx, void* stats, int B, int nh, int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_bert_attn_bwd(const void* qkv, const void* dctx, const void* ctx, const long long* mask, const void* stats, void* dqkv, int B, int nh, int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 /* packed (unpadded) sequences -- BERT with the padded positions dropped (they feed neither the pooler's CLS row nor any
    kept row: masked keys), reference HF BertModel via bert_hugface.py:20 / two_stream.py:178-179: sequence b's rows are
-   seq[b] .. seq[b+1]-1 (int32 [B+1] prefix offsets, each <= Lmax <= 128 rows) of qkv [rows][3H] / ctx / dqkv, mask the
-   key flag of every packed row (NULL: all keys); stats and the dropout counters keep the padded [B*nh][Lmax] space */
+   seq[b] .. seq[b+1]-1 (int32 [B+1] prefix offsets, each <= Lmax <= 512 rows) of qkv [rows][3H] / ctx / dqkv, mask the
+   key flag of every packed row (NULL: all keys); stats (vcg_bert_attn_stats_bytes(B, nh, Lmax)) and the dropout counters
+   keep the padded [B*nh][Lmax] space */
 VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq, const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_tanh_bwd(int dtype, const void* dy, const void* t, void* dx, long long n, hipStream_t s);

@@ -65,6 +65,8 @@ def main(argv=None):
     torch.cuda.set_device(device)
     model = build_two_stream(clip_frame_num=args.clip_frame_num, seed=args.seed, device=device,
                              precision=args.precision)
+    from vcg_hip.nn import check_max_text_len
+    check_max_text_len(model, args.max_text_len)
     if args.ckpt_path:
         model.load_state_dict(torch.load(args.ckpt_path, map_location=device, weights_only=True)["model_state_dict"])
     model.eval()

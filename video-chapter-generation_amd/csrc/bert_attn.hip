@@ -1,5 +1,5 @@
-// Fused BERT self-attention for the bf16 train / scoring path: one workgroup per (sequence, head), L <= 128 keys,
-// head dim 64, HF BertModel eager-attention semantics (model/lang/bert_hugface.py:20 via two_stream.py:172-179):
+// Fused BERT self-attention for the bf16 train / scoring path: one workgroup per (sequence, head), L <= 128 keys
+// (128 < L <= 512: the tiled kernels of bert_attn_long.hip, dispatched by the entry points below), head dim 64, HF BertModel eager-attention semantics (model/lang/bert_hugface.py:20 via two_stream.py:172-179):
 //
 //   forward : S = Q K^T, P = softmax(scale * S + mask_add) (a row with no valid key is uniform over the L keys, as
 //             HF's finfo.min bias gives), Pd = dropout(P), ctx = Pd V; saved: (row max, 1 / row sum) per query
@@ -16,71 +16,12 @@
 // [col i]). A k-step's 32 k indices only have to be the same SET on both operands, so a D fragment (4 consecutive
 // rows per lane) feeds the next MFMA's operand straight from registers: rows {32s + 4g + r, 32s + 16 + 4g + r} of
 // two adjacent D tiles form lane group g's k-set of k-step s. Only dS crosses waves (through LDS) in the backward.
-#include "common.h"
+#include "bert_attn_tiles.h"
 
 using namespace vcg;
+using namespace vcg::attn;
 
 namespace {
-
-constexpr int LT = 128;  // query / key tile: L <= 128
-constexpr int DH = 64;   // head dim
-constexpr int TP = 136;  // row pitch (elements) of the transposed / square LDS tiles: 272-B rows, conflict-free
-                         // b64 / b128 fragment reads of 16 consecutive rows
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-__device__ __forceinline__ uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
-
-__device__ __forceinline__ uint32_t half16(const uint4& v, int j) {
-  const uint32_t w = (j >> 1) == 0 ? v.x : (j >> 1) == 1 ? v.y : (j >> 1) == 2 ? v.z : v.w;
-  return (j & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
-__device__ __forceinline__ s16x8 frag_rm(const bf16_t* t, int row, int chunk) {  // swizzled [rows][64] tile
-  return *reinterpret_cast<const s16x8*>(t + row * DH + 8 * swz(row, chunk));
-}
-
-// two 8-B halves (elements c0..c0+3 and c0+16..c0+19) of row `row` of a [rows][TP] tile
-__device__ __forceinline__ s16x8 frag_split(const bf16_t* t, int row, int c0) {
-  const uint2 lo = *reinterpret_cast<const uint2*>(t + row * TP + c0);
-  const uint2 hi = *reinterpret_cast<const uint2*>(t + row * TP + c0 + 16);
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 u = {lo.x, lo.y, hi.x, hi.y};
-  return __builtin_bit_cast(s16x8, u);
-}
-
-__device__ __forceinline__ s16x8 pack8(const float (&a)[4], const float (&b)[4]) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 u = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
-  return __builtin_bit_cast(s16x8, u);
-}
-
-__device__ __forceinline__ uint4 ld16(const bf16_t* p, bool ok) {
-  return ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0u, 0u, 0u, 0u);
-}
-
-// rows 4 kg .. 4 kg + 3, 8-element chunk dc of a [L][ld] row-major source (rows >= L zero) -> the transposed tile
-// t[d][row] ([64][TP]); optionally also the swizzled row-major copy rm[row][64]
-__device__ __forceinline__ void load_transpose(const bf16_t* src, long long ld, int L, bf16_t* t, bf16_t* rm, int tid) {
-  const int kg = tid >> 3, dc = tid & 7;
-  uint4 v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = ld16(src + (long long)(4 * kg + e) * ld + 8 * dc, 4 * kg + e < L);
-  if (rm) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int r = 4 * kg + e;
-      *reinterpret_cast<uint4*>(rm + r * DH + 8 * swz(r, dc)) = v[e];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    uint2 q;
-    q.x = half16(v[0], j) | (half16(v[1], j) << 16);
-    q.y = half16(v[2], j) | (half16(v[3], j) << 16);
-    *reinterpret_cast<uint2*>(t + (8 * dc + j) * TP + 4 * kg) = q;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ forward
 // 4 waves; wave w owns queries 32 w .. 32 w + 31. S^T = K Q^T (A = K rows from LDS, B = Q rows from HBM), the
@@ -442,11 +383,19 @@ static int attn_check(const char* fn, const void* qkv, const void* out, const vo
     set_error(std::string(fn) + ": invalid arguments");
     return VCG_ERR_INVALID;
   }
-  if (L > LT) {
-    set_error(std::string(fn) + ": L > 128 is not supported by the fused kernel");
+  if (L > LMAX) {
+    set_error(std::string(fn) + ": L > 512 is not supported by the fused kernels");
     return VCG_ERR_UNSUPPORTED;
   }
   return VCG_OK;
+}
+
+// float2 [B * nh][128] (row max, 1 / row sum) at L <= 128; above it the tiled kernels' layout (bert_attn_tiles.h):
+// the row statistics and the backward's D over the sequence length rounded up to the 128-row tile
+VCG_API long long vcg_bert_attn_stats_bytes(int B, int nh, int L) {
+  if (B < 0 || nh < 0 || L < 0) return 0;
+  const long long Lr = L <= LT ? LT : (L + LT - 1) / LT * LT;
+  return (long long)B * nh * Lr * (long long)(L <= LT ? sizeof(float2) : sizeof(float2) + sizeof(float));
 }
 
 VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx, void* stats, int B, int nh, int L,
@@ -454,8 +403,8 @@ VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx,
   return vcg_bert_attn_fwd_varlen(qkv, mask, nullptr, ctx, stats, B, nh, L, Lp, scale, dropout_p, seed, s);
 }
 
-// Packed (unpadded) sequences: sequence b's rows are seq[b] .. seq[b + 1] - 1 of qkv / ctx (at most Lmax <= 128 of
-// them), mask the key flags of those rows (NULL: every row is a key); stats and the dropout counters keep the padded
+// Packed (unpadded) sequences: sequence b's rows are seq[b] .. seq[b + 1] - 1 of qkv / ctx (at most Lmax <= 512 of
+// them; Lmax > 128: the tiled kernels of bert_attn_long.hip), mask the key flags of those rows (NULL: every row is a key); stats and the dropout counters keep the padded
 // [B][nh][Lmax] index space, so a sequence whose kept rows are a prefix of its padded rows gets the padded result.
 VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
                                      int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
@@ -463,6 +412,7 @@ VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, con
   if (B == 0 || Lmax == 0) return VCG_OK;
   const int rc = attn_check("vcg_bert_attn_fwd", qkv, ctx, stats, B, nh, Lmax, Lp);
   if (rc != VCG_OK) return rc;
+  if (Lmax > LT) return bert_attn_long_fwd(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, scale, dropout_p, seed, s);
   hipLaunchKernelGGL(bert_attn_fwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, mask, (bf16_t*)ctx,
                      (float2*)stats, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
@@ -486,6 +436,9 @@ VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const lo
   }
   const int rc = attn_check("vcg_bert_attn_bwd", qkv, dqkv, stats, B, nh, Lmax, Lp);
   if (rc != VCG_OK) return rc;
+  if (Lmax > LT)  // (the tiled backward keeps its D vector in the stats buffer's tail: vcg_bert_attn_stats_bytes)
+    return bert_attn_long_bwd(qkv, dctx, mask, seq, const_cast<void*>(stats), dqkv, B, nh, Lmax, Lp, scale, dropout_p,
+                              seed, s);
   hipLaunchKernelGGL(bert_attn_bwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, mask,
                      (const float2*)stats, (bf16_t*)dqkv, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());

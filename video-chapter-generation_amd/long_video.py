@@ -169,6 +169,8 @@ def main(argv=None):
     _lib.call("vcg_init", args.gpu)
     model = build_two_stream(clip_frame_num=args.clip_frame_num, head_type=args.head_type, seed=args.seed,
                              device=dev, precision=args.precision).eval()
+    from vcg_hip.nn import check_max_text_len
+    check_max_text_len(model, args.max_text_len)
     if args.bn_mode == "batch":
         from test_video_segment_point import drop_bn_running_stats
         drop_bn_running_stats(model)

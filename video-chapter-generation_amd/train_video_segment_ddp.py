@@ -243,6 +243,8 @@ def main(argv=None):
     test_ds = InferYoutubeClipDataset(SyntheticVideoCorpus(2, H=args.resolution, W=args.resolution, seed=args.seed + 1),
                                       tok, args.clip_frame_num, args.max_text_len)
     model = build_two_stream(clip_frame_num=args.clip_frame_num, seed=args.seed, device=device, precision=args.precision)
+    from vcg_hip.nn import check_max_text_len
+    check_max_text_len(model, args.max_text_len)
     conf = TrainerConfig(max_epochs=args.epoch, batch_size=args.batch_size, val_batch_size=args.batch_size * 8,
                          gradient_accumulation_steps=4, num_workers=0, lr_decay=True,
                          warmup_epochs=args.epoch // 100, final_epochs=args.epoch // 100 * 90, ckpt_path=args.ckpt_path)
@@ -283,6 +285,8 @@ def _window_main(args, rank, world, device, tok):
                                 transform=test_vision_preprocess())
     model = build_window_two_stream(clip_frame_num=args.clip_frame_num, window_size=args.window_size,
                                     head_type=args.head_type, seed=args.seed, device=device, precision=args.precision)
+    from vcg_hip.nn import check_max_text_len
+    check_max_text_len(model, args.max_text_len)
     conf = TrainerConfig(max_epochs=args.epoch, batch_size=args.batch_size, val_batch_size=args.batch_size,
                          gradient_accumulation_steps=4, num_workers=0, lr_decay=True,
                          warmup_epochs=args.epoch // 100, final_epochs=args.epoch // 100 * 90, ckpt_path=args.ckpt_path)

@@ -279,6 +279,8 @@ def main(argv=None):
         train_ds = YoutubeClipDataset(corpus, tok, args.clip_frame_num, args.max_text_len, mode=args.data_mode)
         test_ds = InferYoutubeClipDataset(test_corpus, tok, args.clip_frame_num, args.max_text_len, mode=args.data_mode)
     model = build_model(args, device)
+    from vcg_hip.nn import check_max_text_len
+    check_max_text_len(model, args.max_text_len)
     writer = None
     if args.tensorboard_log:
         from common_utils.scalar_log import summary_writer

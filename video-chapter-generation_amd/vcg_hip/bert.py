@@ -3,9 +3,9 @@ hand-written backward.
 
 Reference use: TwoStream.forward -> lang_model(input_ids, attention_mask).pooler_output
 (model/fusion/two_stream.py:172-179) with lang_model = BertModel('bert-base-uncased')
-(model/lang/bert_hugface.py:20). Per layer: fused QKV GEMM -> attention (bf16, L <= 128: ONE fused
-kernel per direction, bert_attn.hip, nothing L x L in HBM; otherwise batched QK^T -> masked softmax (+dropout) ->
-batched PV) -> out-proj GEMM -> LN(dropout(.)+res) -> FFN1 GEMM with erf-GELU
+(model/lang/bert_hugface.py:20). Per layer: fused QKV GEMM -> attention (bf16, L <= 512: fused kernels,
+nothing L x L in HBM -- one per direction at L <= 128, bert_attn.hip; 128 x 128 tiles with an online softmax above
+it, bert_attn_long.hip; otherwise batched QK^T -> masked softmax (+dropout) -> batched PV) -> out-proj GEMM -> LN(dropout(.)+res) -> FFN1 GEMM with erf-GELU
 epilogue -> FFN2 GEMM -> LN(dropout(.)+res); pooler = tanh(W h[:,0] + b).
 
 Unpadded sequences (Packing, bf16 with the fused attention, callers that read only the pooler output -- TwoStream,
@@ -153,7 +153,8 @@ class PackingRequest:
 
 
 class BertEncoderEngine:
-    # bf16 L <= 128: the fused attention kernels (bert_attn.hip); False: the unfused kernels (tests compare both)
+    # bf16 L <= 512: the fused attention kernels (bert_attn.hip, bert_attn_long.hip); False: the unfused kernels at
+    # every L (tests compare both)
     fused_attn = True
     # unpadded sequences (Packing) where the caller reads only the pooler output and the fused attention applies;
     # False: every padded row is computed (tests compare both)
@@ -181,7 +182,7 @@ class BertEncoderEngine:
 
     def _fused_attn(self, L, dh):
         # (the fp32 parity mode always runs unfused)
-        return self.dtype == torch.bfloat16 and L <= 128 and dh == 64 and BertEncoderEngine.fused_attn
+        return self.dtype == torch.bfloat16 and L <= 512 and dh == 64 and BertEncoderEngine.fused_attn
 
     def _w(self, p):
         return self.flat.compute_view(p, self.dtype)
@@ -220,6 +221,9 @@ class BertEncoderEngine:
             packing = self.packing
         cfg = m.config
         B, L = ids.shape
+        if L > cfg.max_position_embeddings:  # (the embedding kernel indexes the position table by position)
+            raise ValueError(f"BertModel: text length {L} exceeds max_position_embeddings "
+                             f"{cfg.max_position_embeddings}")
         H = cfg.hidden_size
         nh = cfg.num_attention_heads
         dh = H // nh
@@ -444,15 +448,15 @@ class _WSide:
 
 def attention_fwd(qkv_buf, mask, B, nh, L, Lp, dh, scale, p_a, seed, fused, seq=None, rows=None):
     """ctx [B*L, H] of HF BertSelfAttention (eager) from the fused projection qkv_buf [B*L (+8), 3H] and the
-    key mask [B, L]; returns (ctx, saved-for-backward). fused: bert_attn.hip (bf16, L <= 128, dh = 64: one kernel,
-    row statistics saved); else QK^T GEMM -> masked softmax (+dropout) -> PV GEMM with S, P, Pd in HBM.
+    key mask [B, L]; returns (ctx, saved-for-backward). fused: bert_attn.hip / bert_attn_long.hip (bf16, L <= 512,
+    dh = 64: only per-query row statistics saved); else QK^T GEMM -> masked softmax (+dropout) -> PV GEMM with S, P, Pd in HBM.
     seq: packed sequences (Packing.seq; fused only), `rows` rows, mask = the packed rows' key flags."""
     H = nh * dh
     rows = B * L if rows is None else rows
     dt, dev = qkv_buf.dtype, qkv_buf.device
     ctx = torch.empty((rows, H), dtype=dt, device=dev)
     if fused:
-        stats = torch.empty((B * nh * 128, 2), dtype=torch.float32, device=dev)
+        stats = ops.bert_attn_stats(B, nh, L, dev)
         ops.bert_attn_fwd(qkv_buf, mask, ctx, stats, B, nh, L, Lp, scale, p_a, seed, seq=seq)
         return ctx, dict(stats=stats)
     assert seq is None, "packed sequences need the fused attention"

@@ -321,8 +321,15 @@ class BertModel(NativeRoot, nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
+    def check_text_len(self, L):
+        """A text longer than the position table would read past it (vcg_embed_ln_fwd indexes it by position)."""
+        P = self.config.max_position_embeddings
+        if L > P:
+            raise ValueError(f"BertModel: text length {L} exceeds max_position_embeddings {P}")
+
     def native_forward(self, input_ids, attention_mask, hooks=None):
         """Returns (pooled, last_hidden) in the compute dtype (autograd-connected)."""
+        self.check_text_len(input_ids.shape[-1])
         from .bert import BertEncoderEngine
         from .functions import BertFn
         f = self.native_flat()
@@ -336,5 +343,14 @@ class BertModel(NativeRoot, nn.Module):
         if token_type_ids is not None and bool((token_type_ids != 0).any()):
             raise NotImplementedError("native BertModel supports token_type_ids == 0 (the reference passes none)")
         B, L = input_ids.shape
+        self.check_text_len(L)
         pooled, last = self.native_forward(input_ids, attention_mask)
         return BertOutput(last.view(B, L, -1), pooled)
+
+
+def check_max_text_len(model, max_text_len):
+    """Drivers: --max_text_len against the position table of every BertModel inside `model`, before any data is built."""
+    for m in model.modules():
+        if isinstance(m, BertModel) and max_text_len > m.config.max_position_embeddings:
+            raise SystemExit(f"error: --max_text_len {max_text_len} exceeds the language model's "
+                             f"{m.config.max_position_embeddings} positions (BertConfig.max_position_embeddings)")

@@ -757,8 +757,15 @@ def attn_softmax_bwd(dPd, Pm, dS, Z, L, Lp, scale, p=0.0, seed=0):
               int(seed) & (2**64 - 1), stream())
 
 
+def bert_attn_stats(B, nh, L, device):
+    """The fused attention's saved state (f32, vcg_bert_attn_stats_bytes: the row statistics the forward writes; at
+    L > 128 also the backward's D vector)."""
+    return torch.empty(_lib.query("vcg_bert_attn_stats_bytes", B, nh, L) // 4, dtype=torch.float32, device=device)
+
+
 def bert_attn_fwd(qkv, mask, ctx, stats, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None):
-    """Fused attention forward (bf16): qkv [B*L(+pad), 3H] -> ctx [B*L, H]; stats [B*nh*128, 2] f32.
+    """Fused attention forward (bf16, L <= 512, head dim 64; L > 128: the tiled online-softmax kernels): qkv
+    [B*L(+pad), 3H] -> ctx [B*L, H]; stats: bert_attn_stats(B, nh, L).
     seq (int32 [B+1]): packed sequences, rows seq[b] .. seq[b+1]-1 (L = the longest, mask = the packed rows' key
     flags; vcg_bert_attn_fwd_varlen)."""
     if seq is None:
@@ -770,6 +777,8 @@ def bert_attn_fwd(qkv, mask, ctx, stats, B, nh, L, Lp, scale, p=0.0, seed=0, seq
 
 
 def bert_attn_bwd(qkv, dctx, ctx, mask, stats, dqkv, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None):
+    """Backward of bert_attn_fwd: dqkv [B*L, 3H] = dQ | dK | dV (deterministic; ctx may be None). At L > 128 it writes
+    its D vector into the tail of `stats`."""
     if seq is None:
         _lib.call("vcg_bert_attn_bwd", P(qkv), P(dctx), P(ctx), P(mask), P(stats), P(dqkv), B, nh, L, Lp, float(scale),
                   float(p), int(seed) & (2**64 - 1), stream())

@@ -353,7 +353,8 @@ VCG_API int vcg_mul_bwd(const float* dout, const float* a, const float* b, float
 /* multi-head attention of short windows (VideoChapterWindowAttention.forward stacked_window_self_attention.py:55-95,
    CrossAttention.forward two_stream_window.py:55-91): per window b, Sq queries over Sk keys (<= 32), nh heads of dh
    (<= 16) columns of row-major q / k / v (leading dims given), scores * scale + bias[h][j] (bias [nh][Pb] or NULL),
-   softmax -> probs [B][nh][Sq][Sk] (saved), dropout, ctx = P V. Backward: dq / dk / dv written, dbias accumulated. */
+   softmax -> probs [B][nh][Sq][Sk] (saved), dropout, ctx = P V. Backward: dq / dk / dv written, dbias accumulated.
+   The backward keeps 2 * nh * Sq * Sk floats in LDS; forward and backward both refuse windows beyond 64 KB of them. */
 VCG_API int vcg_mha_small_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* bias, int Pb, float* ctx, long long ldc, float* probs, int B, int Sq, int Sk, int nh, int dh, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API long long vcg_mha_small_bwd_ws_bytes(int B, int nh, int Pb);
 VCG_API int vcg_mha_small_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* probs, const float* dctx, long long lddc, float* dq, long long lddq, float* dk, long long lddk, float* dv, long long lddv, float* dbias, int Pb, float* ws, long long ws_bytes, int B, int Sq, int Sk, int nh, int dh, float scale, float dropout_p, unsigned long long seed, hipStream_t s);

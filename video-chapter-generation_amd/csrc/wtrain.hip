@@ -417,6 +417,9 @@ int ew_grid(long long n) {
   return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);
 }
 
+// LDS of mha_small_bwd_kernel: dS and the dropped probabilities, [nh][Sq][Sk] floats each
+size_t mha_bwd_lds_bytes(int Sq, int Sk, int nh) { return (size_t)2 * nh * Sq * Sk * sizeof(float); }
+
 int rows_per_block(int rows, int* nb) {
   int n = rows < 512 ? rows : 512;
   if (n < 1) n = 1;
@@ -506,6 +509,8 @@ VCG_API int vcg_mha_small_fwd(const float* q, long long ldq, const float* k, lon
   VCG_REQUIRE(Sq >= 1 && Sq <= vcg::MHA_MAXS && Sk >= 1 && Sk <= vcg::MHA_MAXS, "windows of 1..32 tokens");
   VCG_REQUIRE(dh >= 1 && dh <= vcg::MHA_MAXD && nh >= 1, "head size 1..16");
   VCG_REQUIRE(bias == nullptr || Pb >= Sk, "key bias shorter than the window");
+  // the forward of a training step: refuse what vcg_mha_small_bwd would refuse, before half the step has run
+  VCG_REQUIRE(vcg::mha_bwd_lds_bytes(Sq, Sk, nh) <= 64 * 1024, "window too large for the LDS score buffers");
   if (B <= 0) return VCG_OK;
   VCG_REQUIRE(q && k && v && ctx && probs, "null operand");
   hipLaunchKernelGGL(vcg::mha_small_fwd_kernel, dim3(B), dim3(256), 0, s, q, ldq, k, ldk, v, ldv, bias, Pb, ctx, ldc,
@@ -526,7 +531,7 @@ VCG_API int vcg_mha_small_bwd(const float* q, long long ldq, const float* k, lon
   if (B <= 0) return VCG_OK;
   VCG_REQUIRE(q && k && v && probs && dctx && dq && dk && dv, "null operand");
   if (dbias) VCG_REQUIRE(ws && ws_bytes >= vcg_mha_small_bwd_ws_bytes(B, nh, Pb) && Pb >= Sk, "bias workspace");
-  const size_t lds = (size_t)2 * nh * Sq * Sk * sizeof(float);
+  const size_t lds = vcg::mha_bwd_lds_bytes(Sq, Sk, nh);
   VCG_REQUIRE(lds <= 64 * 1024, "window too large for the LDS score buffers");
   hipLaunchKernelGGL(vcg::mha_small_bwd_kernel, dim3(B), dim3(256), lds, s, q, ldq, k, ldk, v, ldv, probs, dctx, lddc,
                      dq, lddq, dk, lddk, dv, lddv, dbias ? ws : nullptr, Pb, Sq, Sk, nh, dh, scale, dropout_p,

@@ -370,6 +370,28 @@ VCG_API int vcg_linear_small_bwd(const float* g, const float* x, const float* W,
 /* softmax over the C entries of each row (the window model's prob output) */
 VCG_API int vcg_softmax_rows(const float* x, float* out, int rows, int C, hipStream_t s);
 
+/* ---- masked-LM vocabulary head (mlm_head.hip): BertHugface(pretrain_stage=True), model/lang/bert_hugface.py:98-132,
+ *      trained by pretrain_lang_model_hugface.py. bf16 hidden [rows_total][H] and W [V][H] (both K-contiguous, 16-B
+ *      aligned); H a multiple of 8, at most 4096 (VCG_ERR_UNSUPPORTED otherwise, nothing launched); any V. ---------- */
+/* Fused loss of the R rows hidden[rows[i]] (rows NULL: the first R rows) against targets [R] (each in [0, V)):
+   lse [R], row_loss [R] = lse - z_target, mean_loss [1], n_correct [1] = rows whose argmax (lowest index on equal
+   values) is the target; any of the four may be NULL. No R x V tensor is written; ws (vcg_mlm_loss_ws_bytes) holds
+   5 floats per (vocabulary split, row) and 2 per row. Fixed reduction order, no atomics: bit-identical run to run. */
+VCG_API long long vcg_mlm_loss_ws_bytes(int R, int V, int H);
+VCG_API int vcg_mlm_loss_fwd(const void* hidden, int rows_total, const long long* rows, const void* W, const long long* targets, int R, int V, int H, float* ws, long long ws_bytes, float* lse, float* row_loss, float* mean_loss, long long* n_correct, hipStream_t stream);
+/* dZ (bf16 [R][ldz], ldz = V rounded up to 8, pad columns zero) = (exp(z - lse) - onehot(target)) * dloss[0] / R,
+   the logits recomputed; dloss is a device scalar */
+VCG_API int vcg_mlm_loss_bwd(const void* hidden, int rows_total, const long long* rows, const void* W, const long long* targets, const float* lse, const float* dloss, int R, int V, int H, void* dZ, long long ldz, hipStream_t stream);
+/* logits (fp32 [rows][ldz], ldz = V rounded up to 8, pad columns zero) = hidden W^T: the drop-in forward */
+VCG_API int vcg_mlm_logits(const void* hidden, int rows, const void* W, int V, int H, float* logits, long long ldz, hipStream_t stream);
+/* fp32 parity mode: the same reduction of logits [R][ldz] that are in memory (ws: 7 * R floats), and dZ in place
+   (columns V .. ldz - 1 zeroed) */
+VCG_API int vcg_mlm_reduce_f32(const float* logits, long long ldz, const long long* targets, int R, int V, float* ws, long long ws_bytes, float* lse, float* row_loss, float* mean_loss, long long* n_correct, hipStream_t stream);
+VCG_API int vcg_mlm_dz_f32(float* logits, long long ldz, const float* lse, const long long* targets, const float* dloss, int R, int V, hipStream_t stream);
+/* prob[b][l][v] = softmax over l of logits [B][L][ldz] (F.softmax(logits, dim=1), bert_hugface.py:114); prob rows of
+   ldp floats */
+VCG_API int vcg_seq_softmax_fwd(const float* logits, long long ldz, float* prob, long long ldp, int B, int L, int V, hipStream_t stream);
+
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148
  * (bucketed gradient all-reduce on every backward) and the parameter broadcast of :261-263. One communicator per

@@ -1,0 +1,134 @@
+"""Drop-in for reference data/youtube_subtitle_dataset.py `YoutubeClipSubtitleDatasetForHugFace` (:248-408), the
+masked-LM pre-training sampler of pretrain_lang_model_hugface.py: same constructor, same sample tuple, same rules.
+
+    YoutubeClipSubtitleDatasetForHugFace(data_file, vid_file, model_type, tokenizer, clip_frame_num, max_text_len,
+                                         subtitle_dir=None, transform=None, target_transform=None)
+    item i -> (text_ids i64 [L], targets i64 [L] (-1 = not masked), attention_mask i64 [L])
+
+- item i draws one clip centre t of video i with Python `random` from [T/2, image_num - T/2), image_num =
+  round(duration - 1) (:293, :309-314);
+- the text is every subtitle starting inside (t - T/2 - 4, t + T/2 + 4), joined by spaces (:317-326);
+- `bert` branch (:349-402): "[CLS] " + text, tokenised, truncated to max_text_len, masked by `mask_tokens`, padded
+  with "[PAD]" (attention mask 0), converted to ids; the targets are the original ids at the masked positions;
+- `gpt` (next-token targets, :329-347) is outside this port: the constructor raises.
+
+`SyntheticSubtitleDatasetForHugFace` runs the same sampler over data/synthetic_dataset.py's corpus, so the driver runs
+with no data on disk.
+"""
+import json
+import os
+import random
+
+import numpy as np
+import torch
+
+from .common_utils import parse_csv_to_list
+from .youtube_dataset import subtitle_files
+
+X_PAD = 0
+Y_PAD = -1
+TEXT_EXTRA_TIME_GAP = 4
+
+
+def mask_tokens(tokens, rng):
+    """The masking rule of :356-380 on a token list whose position 0 ([CLS]) is never masked; `rng` is the `random`
+    module or a random.Random, consumed call for call as the reference consumes `random`. Returns (the masked token
+    list, {position: original token}).
+
+    round(n * 0.15) of the n = len(tokens) - 1 maskable positions are drawn (Python's round: n <= 3 gives none) and
+    set to "[MASK]"; 10 % of those are then drawn to stay unmasked and 10 % to be replaced. Two quirks are kept:
+    the reference's "restore" loop assigns each such token to itself, so the positions drawn to stay unmasked stay
+    "[MASK]" (the draw still advances the generator); and each replacement is sampled from the token list as it
+    stands after masking, "[MASK]" and "[CLS]" included."""
+    tokens = list(tokens)
+    positions = list(range(1, len(tokens)))
+    masked = rng.sample(positions, round(len(positions) * 0.15))
+    rng.sample(masked, round(len(masked) * 0.1))  # the "not masked" draw: without effect, see above
+    replaced = rng.sample(masked, round(len(masked) * 0.1))
+    original = {}
+    for pos in masked:
+        original[pos] = tokens[pos]
+        tokens[pos] = "[MASK]"
+    for pos in replaced:
+        tokens[pos] = rng.sample(tokens, 1)[0]
+    return tokens, original
+
+
+def clip_text(subtitles, t, half_clip_frame_num):
+    """Subtitles starting strictly inside (clip start - 4 s, clip end + 4 s) of the clip centred at t (:313-326)."""
+    lo = t - half_clip_frame_num - TEXT_EXTRA_TIME_GAP
+    hi = t + half_clip_frame_num + TEXT_EXTRA_TIME_GAP
+    text = ""
+    for sub in subtitles:
+        if lo < sub["start"] < hi:
+            text = text + " " + sub["text"] if text else sub["text"]  # (no separator while the text is still empty)
+    return text
+
+
+def encode_mlm(tokenizer, text, max_text_len, rng):
+    """:349-402 -> (ids, targets, attention_mask) as int64 tensors of max_text_len."""
+    tokens = tokenizer.tokenize("[CLS] " + text)[:max_text_len]
+    tokens, original = mask_tokens(tokens, rng)
+    n_pad = max(0, max_text_len - len(tokens))
+    mask = [1] * len(tokens) + [0] * n_pad
+    tokens = tokens + ["[PAD]"] * n_pad
+    ids = tokenizer.convert_tokens_to_ids(tokens)
+    y = [Y_PAD] * len(tokens)
+    for pos, tok in original.items():
+        y[pos] = tokenizer.convert_tokens_to_ids([tok])[0]
+    return tuple(torch.from_numpy(np.array(a)).long() for a in (ids, y, mask))
+
+
+def _check_model_type(model_type):
+    if model_type != "bert":
+        raise RuntimeError(f"model_type {model_type!r}: only the reference's 'bert' (masked-LM) branch is built here")
+
+
+class YoutubeClipSubtitleDatasetForHugFace(torch.utils.data.Dataset):
+    def __init__(self, data_file, vid_file, model_type, tokenizer, clip_frame_num, max_text_len, subtitle_dir=None,
+                 transform=None, target_transform=None):
+        _check_model_type(model_type)
+        self.model_type = model_type
+        self.tokenizer = tokenizer
+        self.clip_frame_num = clip_frame_num
+        self.half_clip_frame_num = int(clip_frame_num // 2)
+        self.max_text_len = max_text_len
+        vids, titles, durations, timestamps = parse_csv_to_list(data_file)
+        self.vid2title = dict(zip(vids, titles))
+        self.vid2timestamps = dict(zip(vids, timestamps))
+        self.vid2durations = dict(zip(vids, durations))
+        with open(vid_file) as f:
+            self.vids = [x.strip() for x in f.readlines()]
+        self.vid2asr_files = subtitle_files(os.path.dirname(data_file) if subtitle_dir is None else subtitle_dir)
+        self.transform = transform
+        self.target_transform = target_transform
+
+    def __len__(self):
+        return len(self.vids)
+
+    def __getitem__(self, i):
+        vid = self.vids[i]
+        image_num = round(self.vid2durations[vid] - 1)
+        with open(self.vid2asr_files[vid]) as f:
+            subtitles = json.load(f)
+        h = self.half_clip_frame_num
+        t = random.sample(list(range(h, image_num - h)), k=1)[0]
+        return encode_mlm(self.tokenizer, clip_text(subtitles, t, h), self.max_text_len, random)
+
+
+class SyntheticSubtitleDatasetForHugFace(torch.utils.data.Dataset):
+    """The same sampler over a data.synthetic_dataset.SyntheticVideoCorpus (image_num frames at 1 fps)."""
+
+    def __init__(self, corpus, model_type, tokenizer, clip_frame_num, max_text_len):
+        _check_model_type(model_type)
+        self.c, self.tokenizer, self.max_text_len = corpus, tokenizer, max_text_len
+        self.half_clip_frame_num = int(clip_frame_num // 2)
+
+    def __len__(self):
+        return len(self.c.vids)
+
+    def __getitem__(self, i):
+        vid = self.c.vids[i]
+        h = self.half_clip_frame_num
+        t = random.sample(list(range(h, self.c.image_num[vid] - h)), k=1)[0]
+        return encode_mlm(self.tokenizer, clip_text(self.c.subtitles[vid], t, h), self.max_text_len, random)

@@ -13,8 +13,38 @@ import io
 from . import synth
 
 
+def build_mlm_model(seed=None, device=None, precision="bf16", dropout=None):
+    """The pre-training driver's model (pretrain_lang_model_hugface.py:237): BertHugface() with its vocabulary head."""
+    from model.lang.bert_hugface import BertHugface
+    from vcg_hip.nn import BertConfig
+    cfg = BertConfig(output_attentions=True)
+    if dropout is not None:
+        cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = dropout
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = BertHugface(pretrain_stage=True, config=cfg)
+    if device is not None:
+        model = model.to(device)
+    if seed is not None:
+        synth.init_params(model, seed)
+    model.precision = precision
+    return model
+
+
+def load_lang_pretrain(bert, path):
+    """The hand-off of train_video_segment_point.py:326-330: the language model starts from the masked-LM stage's
+    checkpoint (pretrain_lang_model_hugface.py's checkpoint["model_state_dict"], a BertHugface state dict with its
+    vocabulary head). `bert` is the scorer's BertModel; its weights become the checkpoint's base_model.*, strictly."""
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
+    V, H = bert.config.vocab_size, bert.config.hidden_size
+    if "head.weight" not in sd or tuple(sd["head.weight"].shape) != (V, H):
+        raise ValueError(f"{path}: not a masked-LM pre-training checkpoint (no [{V}, {H}] head.weight)")
+    pre = "base_model."
+    bert.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}, strict=True)
+
+
 def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropout=None, seed=None, device=None,
-                     precision="fp32", bn_stats=None):
+                     precision="fp32", bn_stats=None, lang_pretrain_ckpt=None):
     from model.fusion.two_stream import TwoStream
     from model.lang.bert_hugface import BertHugface
     from model.vision.resnet50_tsm import Resnet50TSM
@@ -36,6 +66,8 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
         model = model.to(device)
     if seed is not None:
         synth.init_params(model, seed)  # on the GPU this runs the HIP generator (bit-identical to numpy)
+    if lang_pretrain_ckpt:  # (after the seeded init, which covers every parameter)
+        load_lang_pretrain(model.lang_model, lang_pretrain_ckpt)
     if bn_stats is not None:
         synth.load_bn_stats(model, bn_stats)
     model.precision = precision
@@ -43,11 +75,13 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
 
 
 def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="mlp", model_type="r50tsm", seed=None,
-                device=None, precision="bf16", dropout=None):
+                device=None, precision="bf16", dropout=None, lang_pretrain_ckpt=None):
     """The driver's model by `--data_mode` (`train_video_segment_point.py:330-363`): "text" ->
-    BertHugface + head, "image" -> Resnet50TSM (or Resnet50) + head, "all" -> TwoStream."""
+    BertHugface + head, "image" -> Resnet50TSM (or Resnet50) + head, "all" -> TwoStream. lang_pretrain_ckpt: the
+    masked-LM stage's checkpoint for the language model (`:326-330`; "all" and "text")."""
     if data_mode == "all":
-        return build_two_stream(clip_frame_num, hidden_size, head_type, dropout, seed, device, precision)
+        return build_two_stream(clip_frame_num, hidden_size, head_type, dropout, seed, device, precision,
+                                lang_pretrain_ckpt=lang_pretrain_ckpt)
     if data_mode == "text":
         from model.lang.bert_hugface import BertHugface
         from vcg_hip.nn import BertConfig
@@ -72,6 +106,10 @@ def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="
         model = model.to(device)
     if seed is not None:
         synth.init_params(model, seed)
+    if lang_pretrain_ckpt:
+        if data_mode != "text":
+            raise ValueError("lang_pretrain_ckpt: the image-only model has no language model")
+        load_lang_pretrain(model.base_model, lang_pretrain_ckpt)
     model.precision = precision
     return model
 

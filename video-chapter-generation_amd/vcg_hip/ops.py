@@ -861,6 +861,86 @@ def cross_entropy_bwd(logits, labels, dloss):
     return dlogits
 
 
+# ----------------------------------------------------------------------------- masked-LM head (mlm_head.hip)
+def mlm_vp(V):
+    """Row stride of the dZ / logits buffers: V rounded up to 16-byte rows."""
+    return (V + 7) // 8 * 8
+
+
+def _mlm_outputs(R, device):
+    return (torch.empty(R, dtype=torch.float32, device=device), torch.empty(R, dtype=torch.float32, device=device),
+            torch.empty((), dtype=torch.float32, device=device), torch.empty((), dtype=torch.int64, device=device))
+
+
+def mlm_loss_fwd(hidden, rows, W, targets, workspace=None):
+    """Fused masked-LM loss of hidden[rows] (bf16 [rows_total, H], rows int64 [R] or None) against W (bf16 [V, H]) and
+    targets (int64 [R], in [0, V)): (lse [R], row_loss [R], mean_loss [], n_correct [] int64)."""
+    _chk(hidden, torch.bfloat16, "hidden")
+    _chk(W, torch.bfloat16, "W")
+    _chk(targets, torch.int64, "targets")
+    if rows is not None:
+        _chk(rows, torch.int64, "rows")
+    R, (V, H) = targets.numel(), W.shape
+    nbytes = _lib.query("vcg_mlm_loss_ws_bytes", R, V, H)
+    if workspace is None:
+        workspace = ws(nbytes, hidden.device)
+    lse, row_loss, loss, n_correct = _mlm_outputs(R, hidden.device)
+    _lib.call("vcg_mlm_loss_fwd", P(hidden), hidden.shape[0], P(rows), P(W), P(targets), R, V, H, P(workspace),
+              workspace.numel() * 4, P(lse), P(row_loss), P(loss), P(n_correct), stream())
+    return lse, row_loss, loss, n_correct
+
+
+def mlm_loss_bwd(hidden, rows, W, targets, lse, dloss):
+    """dZ (bf16 [R, mlm_vp(V)], pad columns zero) = (softmax(z) - onehot(target)) * dloss / R; dloss a device scalar."""
+    _chk(dloss, torch.float32, "dloss")
+    R, (V, H) = targets.numel(), W.shape
+    dZ = torch.empty((R, mlm_vp(V)), dtype=torch.bfloat16, device=hidden.device)
+    _lib.call("vcg_mlm_loss_bwd", P(hidden), hidden.shape[0], P(rows), P(W), P(targets), P(lse), P(dloss), R, V, H,
+              P(dZ), dZ.shape[1], stream())
+    return dZ
+
+
+def mlm_logits(hidden, W):
+    """fp32 logits [rows, mlm_vp(V)] (pad columns zero) = hidden W^T, bf16 operands."""
+    _chk(hidden, torch.bfloat16, "hidden")
+    _chk(W, torch.bfloat16, "W")
+    V, H = W.shape
+    out = torch.empty((hidden.shape[0], mlm_vp(V)), dtype=torch.float32, device=hidden.device)
+    _lib.call("vcg_mlm_logits", P(hidden), hidden.shape[0], P(W), V, H, P(out), out.shape[1], stream())
+    return out
+
+
+def mlm_reduce_f32(logits, V, targets):
+    """The fused loss' outputs from fp32 logits [R, ld >= V] that are in memory (the fp32 parity mode)."""
+    _chk(logits, torch.float32, "logits")
+    _chk(targets, torch.int64, "targets")
+    R, ld = logits.shape
+    workspace = ws(7 * R * 4, logits.device)  # 5 floats per row of partials + 2 of row results
+    lse, row_loss, loss, n_correct = _mlm_outputs(R, logits.device)
+    _lib.call("vcg_mlm_reduce_f32", P(logits), ld, P(targets), R, V, P(workspace), workspace.numel() * 4, P(lse),
+              P(row_loss), P(loss), P(n_correct), stream())
+    return lse, row_loss, loss, n_correct
+
+
+def mlm_dz_f32(logits, V, lse, targets, dloss):
+    """In place: logits [R, ld] -> dZ (columns V .. ld - 1 zeroed)."""
+    _chk(logits, torch.float32, "logits")
+    _chk(dloss, torch.float32, "dloss")
+    R, ld = logits.shape
+    _lib.call("vcg_mlm_dz_f32", P(logits), ld, P(lse), P(targets), P(dloss), R, V, stream())
+    return logits
+
+
+def seq_softmax_fwd(logits, B, L, V, ldz=None):
+    """prob [B, L, V] = softmax over L of fp32 logits [B, L, ldz] (F.softmax(logits, dim=1))."""
+    if logits.dtype != torch.float32 or not logits.is_cuda:
+        raise RuntimeError("seq_softmax_fwd: fp32 GPU logits")
+    ldz = ldz if ldz is not None else V
+    prob = torch.empty((B, L, V), dtype=torch.float32, device=logits.device)
+    _lib.call("vcg_seq_softmax_fwd", P(logits), ldz, P(prob), V, B, L, V, stream())
+    return prob
+
+
 # ----------------------------------------------------------------------------- optimiser
 def sumsq(x, out, workspace=None):
     if workspace is None:

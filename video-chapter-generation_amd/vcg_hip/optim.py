@@ -37,16 +37,18 @@ def param_groups(model, weight_decay):
     ]
 
 
-def configure_adamw(model, train_config):
+def configure_adamw(model, train_config, skip=()):
+    """skip: parameters the step leaves bit-unchanged, like those with requires_grad False (no update, no decay)."""
     groups = param_groups(model, train_config.weight_decay)
-    return FusedAdamW(groups, lr=train_config.learning_rate, betas=train_config.betas, model=model)
+    return FusedAdamW(groups, lr=train_config.learning_rate, betas=train_config.betas, model=model, skip=skip)
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip=()):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self.model = model
+        self._skip = {id(p) for p in skip}
         self._flat = None
         self._m = self._v = None
         self._flags = None
@@ -78,7 +80,7 @@ class FusedAdamW(torch.optim.Optimizer):
         for g in self.param_groups:
             code = 1 if g["weight_decay"] != 0.0 else 0
             for p in g["params"]:
-                if not p.requires_grad:
+                if not p.requires_grad or id(p) in self._skip:
                     continue
                 o = f.offset_of(p)
                 flags[o // flatmod.ALIGN:(o + p.numel() + flatmod.ALIGN - 1) // flatmod.ALIGN] = code

@@ -264,6 +264,12 @@ VCG_API int vcg_tsm_unshift_add(int dtype, const void* dshift, const void* other
 /* ---- BERT support (bert.hip) ------------------------------------------------------------- */
 VCG_API int vcg_embed_ln_fwd(int dtype, const long long* ids, const float* word, const float* pos, const float* type, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int B, int L, int H, float eps, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API long long vcg_ln_bwd_ws_bytes(int rows, int H);
+/* embedding backward: LayerNorm backward, then word / position / token-type gradients accumulated (fp32, fixed order,
+   no atomics; word_grad / pos_grad / type_grad may be NULL; row pad_idx of word_grad is never written, pad_idx < 0:
+   none). ws: vcg_ln_bwd_ws_bytes(B * L, H) bytes. H <= 1024.
+   Requires L <= 2 * row blocks, row blocks = ceil(rows / ceil(rows / 512)), rows = B * L (every BERT shape, L <= 512,
+   meets it): the [L][H] per-position sums reuse the
+   [row blocks][2][H] partial region; a longer single sequence is VCG_ERR_INVALID. */
 VCG_API int vcg_embed_ln_bwd(int dtype, const void* dout, const long long* ids, const float* word, const float* pos, const float* type, const float* gamma, const float* mean, const float* rstd, float* word_grad, float* pos_grad, float* type_grad, float* gamma_grad, float* beta_grad, float* ws, long long ws_bytes, int B, int L, int H, float dropout_p, unsigned long long seed, long long pad_idx, hipStream_t s);
 VCG_API int vcg_ln_fwd(int dtype, const void* x, const void* res, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int rows, int H, float eps, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_ln_bwd(int dtype, const void* dout, const void* x, const void* res, const float* gamma, const float* mean, const float* rstd, void* dx, void* dres, float* gamma_grad, float* beta_grad, float* bias_grad, float* ws, long long ws_bytes, int rows, int H, float dropout_p, unsigned long long seed, hipStream_t s);

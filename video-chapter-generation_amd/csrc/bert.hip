@@ -808,6 +808,8 @@ VCG_API int vcg_embed_ln_bwd(int dtype, const void* dout, const long long* ids, 
   if (dtype & VCG_GRAD_F32) dtype = VCG_F32;  // (only dout is read in the storage dtype here)
   int rpb;
   const int nb = row_blocks(rows, &rpb);
+  // the [L][H] per-position sums reuse the [nb][2][H] partial region in front of de (every BERT shape: L <= 512)
+  VCG_REQUIRE(L <= 2 * nb, "L > 2 * row blocks: the per-position sums would not fit the partial region");
   float* part = ws;
   float* de = ws + (long long)nb * 2 * H;
   if (dtype == VCG_BF16)
@@ -825,7 +827,7 @@ VCG_API int vcg_embed_ln_bwd(int dtype, const void* dout, const long long* ids, 
                        pad_idx);
     VCG_LAUNCH_CHECK();
   }
-  // the partial region is free again: reuse it for the per-position sums (2*nb >= L since rows >= L)
+  // the partial region is free again: reuse it for the per-position sums (L <= 2 * nb, required above)
   hipLaunchKernelGGL(embed_pos_kernel, dim3((H + 255) / 256, L), dim3(256), 0, s, de, pos_grad, part, B, L, H);
   VCG_LAUNCH_CHECK();
   if (type_grad) {

@@ -305,7 +305,10 @@ VCG_API int vcg_head_mlp_bwd(int dtype, const void* Vout, const void* Lout, cons
 /* ChapterHead head_type "attn" (head_attn.hip; also the window ChapterHead "self_attn", O = hid <= 256): SelfAttention(hid, n_head, O) (two_stream.py:8-48) over the T+1
  * fused tokens cat([Vout [B*T][hid], Lout [B][hid]]) of each window, output proj of token 0, softmax. Weights are
  * the fp32 nn.Linear parameters ([out][in]). `saved` (f32, vcg_head_attn_saved_floats) keeps the state of the
- * backward; dropout_p = attn_drop.p in training (counter-hash mask, regenerated by the backward with `seed`). */
+ * backward; dropout_p = attn_drop.p in training (counter-hash mask, regenerated by the backward with `seed`).
+ * Limits: T + 1 <= 64, hid <= 256 divisible by n_head <= 16, O <= 256, and a window's state must fit the 64 KB of
+ * LDS a workgroup may ask for: (3 (T+1) hid + 2 hid + n_head (T+1)) * 4 bytes <= 65536 (with 4 heads: T <= 19 at
+ * hid 256, T <= 40 at hid 128). Forward and backward refuse anything beyond with VCG_ERR_INVALID, before any launch. */
 VCG_API long long vcg_head_attn_saved_floats(int B, int T, int hid, int nh);
 VCG_API int vcg_head_attn_fwd(int dtype, const void* Vout, const void* Lout, const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv, const float* Wp, const float* bp, float* saved, long long saved_floats, float* logits, float* prob, int B, int T, int hid, int nh, int O, float dropout_p, unsigned long long seed, hipStream_t s);
 /* dVout / dLout = ReLU-masked input gradients (relu_mask: the projections' ReLU); parameter grads (nullable)

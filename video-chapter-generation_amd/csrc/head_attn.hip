@@ -10,9 +10,11 @@
 // Only token 0's query row reaches the output, so the forward computes k, v for all T+1 tokens but q
 // for token 0 only, and the backward sends query gradients to token 0 only: the same function, less
 // work. One workgroup per clip window owns the whole per-window computation (T+1 <= 64 tokens,
-// hid <= 256): the head is launch-bound (~0.05 GFLOP per 64 windows), so everything between the two
-// projection GEMMs (which run on the MFMA engine) is ONE launch forward and ONE backward, plus the
-// parameter-gradient column reductions (deterministic, no atomics).
+// hid <= 256, and the forward's LDS state of 3 (T+1) hid + 2 hid + n_head (T+1) floats within 64 KB: with
+// 4 heads T <= 19 at hid 256, T <= 40 at hid 128; anything larger is refused before a launch): the head is
+// launch-bound (~0.05 GFLOP per 64 windows), so everything between the two projection GEMMs (which run
+// on the MFMA engine) is ONE launch forward and ONE backward, plus the parameter-gradient column
+// reductions (deterministic, no atomics).
 #include "common.h"
 
 using namespace vcg;
@@ -23,6 +25,18 @@ constexpr int kMaxTok = 64;   // T + 1
 constexpr int kMaxHid = 256;
 constexpr int kMaxHeads = 16;
 constexpr int kMaxOut = 256;  // output_size (2 for the fusion head, hidden for the window self_attn head)
+constexpr long long kMaxLds = 64 * 1024;  // dynamic LDS of one workgroup (nothing here raises the launch limit)
+
+// Dynamic LDS of the forward: X, K, V [T1][hid], q0 / y0 [hid], P [nh][T1] (f32). The backward keeps one
+// [T1][hid] block less and one [nh][T1] block more (nh <= hid), so the forward's request is the larger one.
+long long fwd_lds_bytes(int T, int hid, int nh) {
+  const long long T1 = T + 1;
+  return (3 * T1 * hid + 2 * hid + nh * T1) * (long long)sizeof(float);
+}
+long long bwd_lds_bytes(int T, int hid, int nh) {
+  const long long T1 = T + 1;
+  return (2 * T1 * hid + 2 * hid + 2 * nh * T1) * (long long)sizeof(float);
+}
 
 // token j of window b: vision rows first, then the language row
 template <typename T>
@@ -278,6 +292,8 @@ int check_shapes(int B, int T, int hid, int nh, int O) {
   VCG_REQUIRE(hid > 0 && hid <= kMaxHid && nh > 0 && nh <= kMaxHeads && hid % nh == 0,
               "need hid <= 256 divisible by n_head <= 16");
   VCG_REQUIRE(O > 0 && O <= kMaxOut, "need 1 <= output_size <= 256");
+  VCG_REQUIRE(fwd_lds_bytes(T, hid, nh) <= kMaxLds,
+              "window too large for the 64 KB LDS limit (3 (T+1) hid + 2 hid + n_head (T+1) floats)");
   return VCG_OK;
 }
 
@@ -299,7 +315,7 @@ VCG_API int vcg_head_attn_fwd(int dtype, const void* Vout, const void* Lout, con
   const long long T1 = T + 1, bt = (long long)B * T1 * hid;
   float *X = saved, *K = X + bt, *V = K + bt, *q0 = V + bt, *y0 = q0 + (long long)B * hid,
         *P = y0 + (long long)B * hid;
-  const size_t lds = (size_t)(3 * T1 * hid + 2 * hid + nh * T1) * sizeof(float);
+  const size_t lds = (size_t)fwd_lds_bytes(T, hid, nh);
   if (dtype == VCG_BF16)
     hipLaunchKernelGGL(head_attn_fwd_kernel<bf16_t>, dim3(B), dim3(256), lds, s, (const bf16_t*)Vout,
                        (const bf16_t*)Lout, Wq, bq, Wk, bk, Wv, bv, Wp, bp, X, K, V, q0, P, y0, logits, prob, T, hid,
@@ -329,7 +345,7 @@ VCG_API int vcg_head_attn_bwd(int dtype, const float* saved, const float* Wq, co
   const float *X = saved, *K = X + bt, *V = K + bt, *q0 = V + bt, *y0 = q0 + (long long)B * hid,
               *P = y0 + (long long)B * hid;
   float *dK = ws, *dV = dK + bt, *dq0 = dV + bt;
-  const size_t lds = (size_t)(2 * T1 * hid + 2 * hid + 2 * nh * T1) * sizeof(float);
+  const size_t lds = (size_t)bwd_lds_bytes(T, hid, nh);
   if (dtype == VCG_BF16)
     hipLaunchKernelGGL(head_attn_bwd_kernel<bf16_t>, dim3(B), dim3(256), lds, s, X, K, V, q0, P, Wq, Wk, Wv, Wp,
                        dlogits, dK, dV, dq0, (bf16_t*)dVout, (bf16_t*)dLout, T, hid, nh, O, dropout_p, seed,

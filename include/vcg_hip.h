@@ -401,6 +401,42 @@ VCG_API int vcg_mlm_dz_f32(float* logits, long long ldz, const float* lse, const
    ldp floats */
 VCG_API int vcg_seq_softmax_fwd(const float* logits, long long ldz, float* prob, long long ldp, int B, int L, int V, hipStream_t stream);
 
+/* ---- shot-contrastive (MoCo) pre-training (contrast.hip): model/lang/bert_hugface_constrast.py, trained by
+ *      train_lang/pretrain_constrast_lang_model.py. dtype arguments are vcg_dtype codes of the storage. -------------- */
+/* k = k * m + q * one_minus_m over n fp32 elements (two rounded products, one rounded sum: torch's
+   param_k * m + param_q * (1. - m) bit for bit); k_shadow (bf16, nullable) receives the rounded result */
+VCG_API int vcg_momentum_update(float* k, const float* q, long long n, float m, float one_minus_m, void* k_shadow, hipStream_t stream);
+/* F.normalize(x, dim=1): y = x / max(||x||, eps) on [N][H]; denom [N] (nullable) = max(||x||, eps).
+   Backward: dx (fp32) = (g - y (y . g)) / denom, g fp32, y recomputed from x */
+VCG_API int vcg_l2norm_fwd(int dtype, const void* x, void* y, float* denom, int N, int H, float eps, hipStream_t stream);
+VCG_API int vcg_l2norm_bwd(int dtype, const float* g, const void* x, const float* denom, float* dx, int N, int H, hipStream_t stream);
+/* k0[b] = argmax over c < C of cos(cand[b][c], q[b]) (lowest index on equal values); q [B][H], cand [B][C][H], C <= 64 */
+VCG_API int vcg_contrast_select(int dtype, const void* q, const void* cand, int B, int C, int H, float eps, long long* k0, hipStream_t stream);
+/* The queue: `queue` fp32 [H][K] (the module's buffer) and `queue_km` [K rounded up to 8][H] key-major in km_dtype.
+   enqueue writes keys [N][H] at the device pointer queue_ptr[0] into both and advances it to (ptr + N) % K; K % N != 0
+   is VCG_ERR_INVALID with nothing launched, and a pointer outside [0, K - N] writes nothing. rebuild: queue_km rows
+   0 .. K - 1 = queue^T, rounded to km_dtype. */
+VCG_API int vcg_queue_enqueue(int key_dtype, int km_dtype, const void* keys, float* queue, void* queue_km, long long* queue_ptr, int N, int K, int H, hipStream_t stream);
+VCG_API int vcg_queue_rebuild(int km_dtype, const float* queue, void* queue_km, int K, int H, hipStream_t stream);
+/* out[n * ldo] = scale * a[n] . b[n] (the positive logit) */
+VCG_API int vcg_rowdot(int dtype, const void* a, const void* b, int N, int H, float scale, float* out, long long ldo, hipStream_t stream);
+/* Fused InfoNCE, bf16 q [N][H] and queue_km [K][H] (16-B aligned, H a multiple of 8, at most 4096): the logits are
+   [lpos, q queue_km^T * inv_T], cross-entropy against column 0. lse [N], row_loss [N], mean_loss [1], n_correct [1] =
+   rows whose argmax (lowest index on equal values) is column 0, one_minus_p0 [N] = 1 - softmax(z)[0] formed without
+   cancellation (for the gradient); any of the five may be NULL. Nothing N x K is written; fixed reduction order,
+   bit-identical run to run. */
+VCG_API long long vcg_infonce_ws_bytes(int N, int K, int H);
+VCG_API int vcg_infonce_fwd(const void* q, const void* queue_km, const float* lpos, int N, int K, int H, float inv_T, float* ws, long long ws_bytes, float* lse, float* row_loss, float* one_minus_p0, float* mean_loss, long long* n_correct, hipStream_t stream);
+/* dZ (bf16 [N][ldz], ldz = K rounded up to 8, pad columns zero) = exp(z - lse) * scale over the key columns */
+VCG_API int vcg_infonce_dz(const void* q, const void* queue_km, const float* lse, int N, int K, int H, float inv_T, float scale, void* dZ, long long ldz, hipStream_t stream);
+/* key_logits (fp32 [N][ldz], 16-B aligned, columns K .. K rounded up to 8 zero) = q queue_km^T * inv_T */
+VCG_API int vcg_infonce_logits(const void* q, const void* queue_km, int N, int K, int H, float inv_T, float* key_logits, long long ldz, hipStream_t stream);
+/* fp32 parity mode: the same reduction of key logits that are in memory (ws: 6 * N floats), dZ in place, and the
+   positive's term of the gradient: dq[n] -= one_minus_p0[n] * scale * k[n] */
+VCG_API int vcg_infonce_reduce_f32(const float* key_logits, long long ldz, const float* lpos, int N, int K, float* ws, long long ws_bytes, float* lse, float* row_loss, float* one_minus_p0, float* mean_loss, long long* n_correct, hipStream_t stream);
+VCG_API int vcg_infonce_dz_f32(float* key_logits, long long ldz, const float* lse, float scale, int N, int K, hipStream_t stream);
+VCG_API int vcg_infonce_dq_pos(int dtype, float* dq, const void* k, const float* one_minus_p0, float scale, int N, int H, hipStream_t stream);
+
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148
  * (bucketed gradient all-reduce on every backward) and the parameter broadcast of :261-263. One communicator per

@@ -200,7 +200,8 @@ def build_model(args, device):
     from vcg_hip.build import build_model as _build
     return _build(args.data_mode, clip_frame_num=args.clip_frame_num, hidden_size=128, head_type=args.head_type,
                   model_type=args.model_type, seed=args.seed, device=device, precision=args.precision,
-                  lang_pretrain_ckpt=getattr(args, "lang_pretrain_ckpt", None))
+                  lang_pretrain_ckpt=getattr(args, "lang_pretrain_ckpt", None),
+                  lang_contrast_ckpt=getattr(args, "lang_contrast_ckpt", None))
 
 
 def make_tokenizer(vocab_file):
@@ -254,6 +255,8 @@ def main(argv=None):
     p.add_argument("--ckpt_path", default=None)
     p.add_argument("--lang_pretrain_ckpt", default=None,
                    help="pretrain_lang_model_hugface.py checkpoint the language model starts from (:308,326-330)")
+    p.add_argument("--lang_contrast_ckpt", default=None,
+                   help="train_lang/pretrain_constrast_lang_model.py checkpoint the language model starts from instead")
     # the reference's on-disk corpus (its hard-coded paths, :307-318): frames <img_dir>/<vid>/%05d.jpg, the dataset
     # CSV, the split's vid list, subtitles <subtitle_dir>/*/subtitle_<vid>.json, the validation clip JSON
     p.add_argument("--img_dir", default=None)

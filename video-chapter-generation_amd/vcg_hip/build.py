@@ -43,8 +43,57 @@ def load_lang_pretrain(bert, path):
     bert.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}, strict=True)
 
 
+def build_contrast_model(seed=None, device=None, precision="bf16", dropout=None, K=65536, copy_key=True, m=0.999,
+                         T=0.07, config=None):
+    """The contrastive pre-training driver's model (train_lang/pretrain_constrast_lang_model.py:207):
+    BertHugfaceConstrast(K, m, T). With a seed every parameter and the queue are seeded by name; copy_key (the
+    reference's state: both encoders start from the same weights) copies encoder_q into encoder_k afterwards, False
+    leaves the two seeded differently (tests: a mix-up of the encoders then shows)."""
+    import torch
+    from model.lang.bert_hugface_constrast import BertHugfaceConstrast
+    from vcg_hip.nn import BertConfig
+    cfg = config if config is not None else BertConfig()
+    if dropout is not None:
+        cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = dropout
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = BertHugfaceConstrast(K=K, m=m, T=T, config=cfg)
+    if device is not None:
+        model = model.to(device)
+    if seed is not None:
+        synth.init_params(model, seed)
+        with torch.no_grad():
+            synth.fill(model.queue, synth.KIND_NORMAL, synth.key_of(seed, "queue"), 0.0, 1.0)
+            model.queue.copy_(torch.nn.functional.normalize(model.queue, dim=0))
+            if copy_key:
+                model.encoder_k.load_state_dict(model.encoder_q.state_dict())
+    model.precision = precision
+    return model
+
+
+def load_contrast_pretrain(bert, path):
+    """The contrastive stage's hand-off: `path` is pretrain_constrast_lang_model.py's checkpoint, a bare
+    BertHugfaceConstrast state dict (encoder_q.*, encoder_k.*, queue, queue_ptr). `bert` is the scorer's BertModel; its
+    weights become the checkpoint's encoder_q.*, strictly. Anything else (the masked-LM stage's checkpoint, say) is a
+    ValueError."""
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    pre = "encoder_q."
+    if not isinstance(sd, dict) or "queue" not in sd or not any(k.startswith(pre) for k in sd):
+        raise ValueError(f"{path}: not a contrastive pre-training checkpoint (no queue / encoder_q.* entries)")
+    bert.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}, strict=True)
+
+
+def _load_lang(bert, lang_pretrain_ckpt, lang_contrast_ckpt):
+    if lang_pretrain_ckpt and lang_contrast_ckpt:
+        raise ValueError("lang_pretrain_ckpt and lang_contrast_ckpt: one language-model checkpoint at most")
+    if lang_pretrain_ckpt:
+        load_lang_pretrain(bert, lang_pretrain_ckpt)
+    if lang_contrast_ckpt:
+        load_contrast_pretrain(bert, lang_contrast_ckpt)
+
+
 def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropout=None, seed=None, device=None,
-                     precision="fp32", bn_stats=None, lang_pretrain_ckpt=None):
+                     precision="fp32", bn_stats=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None):
     from model.fusion.two_stream import TwoStream
     from model.lang.bert_hugface import BertHugface
     from model.vision.resnet50_tsm import Resnet50TSM
@@ -66,8 +115,8 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
         model = model.to(device)
     if seed is not None:
         synth.init_params(model, seed)  # on the GPU this runs the HIP generator (bit-identical to numpy)
-    if lang_pretrain_ckpt:  # (after the seeded init, which covers every parameter)
-        load_lang_pretrain(model.lang_model, lang_pretrain_ckpt)
+    # (after the seeded init, which covers every parameter)
+    _load_lang(model.lang_model, lang_pretrain_ckpt, lang_contrast_ckpt)
     if bn_stats is not None:
         synth.load_bn_stats(model, bn_stats)
     model.precision = precision
@@ -75,13 +124,14 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
 
 
 def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="mlp", model_type="r50tsm", seed=None,
-                device=None, precision="bf16", dropout=None, lang_pretrain_ckpt=None):
+                device=None, precision="bf16", dropout=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None):
     """The driver's model by `--data_mode` (`train_video_segment_point.py:330-363`): "text" ->
     BertHugface + head, "image" -> Resnet50TSM (or Resnet50) + head, "all" -> TwoStream. lang_pretrain_ckpt: the
-    masked-LM stage's checkpoint for the language model (`:326-330`; "all" and "text")."""
+    masked-LM stage's checkpoint for the language model (`:326-330`; "all" and "text"); lang_contrast_ckpt: the
+    contrastive stage's instead."""
     if data_mode == "all":
         return build_two_stream(clip_frame_num, hidden_size, head_type, dropout, seed, device, precision,
-                                lang_pretrain_ckpt=lang_pretrain_ckpt)
+                                lang_pretrain_ckpt=lang_pretrain_ckpt, lang_contrast_ckpt=lang_contrast_ckpt)
     if data_mode == "text":
         from model.lang.bert_hugface import BertHugface
         from vcg_hip.nn import BertConfig
@@ -106,10 +156,10 @@ def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="
         model = model.to(device)
     if seed is not None:
         synth.init_params(model, seed)
-    if lang_pretrain_ckpt:
+    if lang_pretrain_ckpt or lang_contrast_ckpt:
         if data_mode != "text":
-            raise ValueError("lang_pretrain_ckpt: the image-only model has no language model")
-        load_lang_pretrain(model.base_model, lang_pretrain_ckpt)
+            raise ValueError("lang_pretrain_ckpt / lang_contrast_ckpt: the image-only model has no language model")
+        _load_lang(model.base_model, lang_pretrain_ckpt, lang_contrast_ckpt)
     model.precision = precision
     return model
 

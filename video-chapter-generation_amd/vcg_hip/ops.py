@@ -941,6 +941,164 @@ def seq_softmax_fwd(logits, B, L, V, ldz=None):
     return prob
 
 
+# ----------------------------------------------------------------------------- MoCo pre-training (contrast.hip)
+NORM_EPS = 1e-12  # F.normalize's default
+
+
+def momentum_update(k, q, m, k_shadow=None):
+    """k = k * m + q * (1. - m) in place over two flat fp32 spans, bit for bit torch's expression: m and 1. - m are
+    formed in double and rounded to fp32 once. k_shadow (bf16, same length) receives the rounded result."""
+    import numpy as np
+    _chk(k, torch.float32, "k")
+    _chk(q, torch.float32, "q")
+    if k.numel() != q.numel() or (k_shadow is not None and k_shadow.numel() != k.numel()):
+        raise ValueError("momentum_update: the spans differ in length")
+    if k_shadow is not None:
+        _chk(k_shadow, torch.bfloat16, "k_shadow")
+    _lib.call("vcg_momentum_update", P(k), P(q), k.numel(), float(np.float32(m)), float(np.float32(1. - m)),
+              P(k_shadow), stream())
+    return k
+
+
+def l2norm_fwd(x, eps=NORM_EPS):
+    """F.normalize(x, dim=1) on [N, H] -> (y in x's dtype, denom fp32 [N] = max(||x||, eps))."""
+    _chk(x, None, "x")
+    N, H = x.shape
+    y = torch.empty_like(x)
+    denom = torch.empty(N, dtype=torch.float32, device=x.device)
+    _lib.call("vcg_l2norm_fwd", dt_code(x.dtype), P(x), P(y), P(denom), N, H, float(eps), stream())
+    return y, denom
+
+
+def l2norm_bwd(g, x, denom):
+    """dx fp32 [N, H] = (g - y (y . g)) / denom."""
+    _chk(g, torch.float32, "g")
+    _chk(x, None, "x")
+    N, H = x.shape
+    dx = torch.empty((N, H), dtype=torch.float32, device=x.device)
+    _lib.call("vcg_l2norm_bwd", dt_code(x.dtype), P(g), P(x), P(denom), P(dx), N, H, stream())
+    return dx
+
+
+def contrast_select(q, cand, eps=NORM_EPS):
+    """k0 int64 [B]: the candidate of cand [B, C, H] with the largest cosine to q [B, H] (lowest index on a tie)."""
+    _chk(q, None, "q")
+    _chk(cand, q.dtype, "cand")
+    B, C, H = cand.shape
+    if q.shape != (B, H):
+        raise ValueError(f"contrast_select: q {tuple(q.shape)} against candidates {tuple(cand.shape)}")
+    k0 = torch.empty(B, dtype=torch.int64, device=q.device)
+    _lib.call("vcg_contrast_select", dt_code(q.dtype), P(q), P(cand), B, C, H, float(eps), P(k0), stream())
+    return k0
+
+
+def queue_kp(K):
+    """Rows of queue_km / row stride of the dZ buffer: K rounded up to 8."""
+    return (K + 7) // 8 * 8
+
+
+def queue_enqueue(keys, queue, queue_km, queue_ptr):
+    """keys [N, H] -> queue[:, ptr:ptr+N] (fp32 [H, K]) and queue_km[ptr:ptr+N] ([queue_kp(K), H]); queue_ptr (device
+    int64 [1]) advances to (ptr + N) % K. K % N != 0 raises with nothing written."""
+    _chk(keys, None, "keys")
+    _chk(queue, torch.float32, "queue")
+    _chk(queue_km, None, "queue_km")
+    _chk(queue_ptr, torch.int64, "queue_ptr")
+    N, H = keys.shape
+    K = queue.shape[1]
+    if queue.shape[0] != H or tuple(queue_km.shape) != (queue_kp(K), H):
+        raise ValueError("queue_enqueue: shapes of queue / queue_km / keys do not agree")
+    _lib.call("vcg_queue_enqueue", dt_code(keys.dtype), dt_code(queue_km.dtype), P(keys), P(queue), P(queue_km),
+              P(queue_ptr), N, K, H, stream())
+
+
+def queue_rebuild(queue, dtype, out=None):
+    """queue fp32 [H, K] -> queue_km [queue_kp(K), H] in `dtype` (transpose + cast; the pad rows are zeros)."""
+    _chk(queue, torch.float32, "queue")
+    H, K = queue.shape
+    if out is None or out.dtype != dtype or tuple(out.shape) != (queue_kp(K), H) or out.device != queue.device:
+        out = torch.zeros((queue_kp(K), H), dtype=dtype, device=queue.device)
+    _lib.call("vcg_queue_rebuild", dt_code(dtype), P(queue), P(out), K, H, stream())
+    return out
+
+
+def rowdot(a, b, scale=1.0, out=None, ldo=1):
+    """out[n * ldo] = scale * a[n] . b[n] (fp32)."""
+    _chk(a, None, "a")
+    _chk(b, a.dtype, "b")
+    N, H = a.shape
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=a.device)
+    _lib.call("vcg_rowdot", dt_code(a.dtype), P(a), P(b), N, H, float(scale), P(out), int(ldo), stream())
+    return out
+
+
+def _nce_outputs(N, device):
+    return (torch.empty(N, dtype=torch.float32, device=device), torch.empty(N, dtype=torch.float32, device=device),
+            torch.empty((), dtype=torch.float32, device=device), torch.empty((), dtype=torch.int64, device=device))
+
+
+def infonce_logits_buffer(N, K, device):
+    """(buf fp32 [N, 4 + queue_kp(K)], the [N, 1 + K] logits view buf[:, 3:4+K]): the positive in column 3, the key
+    columns from the 16-byte aligned column 4."""
+    buf = torch.empty((N, 4 + queue_kp(K)), dtype=torch.float32, device=device)
+    return buf, buf[:, 3:4 + K]
+
+
+def infonce(q, k, queue_km, K, inv_T, want_dq=False, want_logits=False):
+    """InfoNCE of normalised q, k [N, H] against the first K rows of queue_km, logits [q.k, q queue_km^T] * inv_T,
+    label 0 -> (lse [N], row_loss [N], mean loss [], n_correct [] int64, dq fp32 [N, H] or None = d mean loss / dq,
+    logits view [N, 1 + K] or None). bf16: the fused tile kernel (nothing N x K in fp32 unless the logits are asked
+    for); fp32: the logits by vcg_gemm, then reduced."""
+    _chk(q, None, "q")
+    _chk(k, q.dtype, "k")
+    _chk(queue_km, q.dtype, "queue_km")
+    N, H = q.shape
+    Kp = queue_kp(K)
+    if k.shape != q.shape or tuple(queue_km.shape) != (Kp, H):
+        raise ValueError("infonce: shapes of q / k / queue_km do not agree")
+    dev, s = q.device, stream()
+    lse, row_loss, loss, n_correct = _nce_outputs(N, dev)
+    omp0 = torch.empty(N, dtype=torch.float32, device=dev) if want_dq else None  # 1 - p0, free of cancellation
+    scale = inv_T / N
+    logits = dq = None
+    if q.dtype == torch.bfloat16:
+        lpos = rowdot(q, k, inv_T)
+        work = ws(_lib.query("vcg_infonce_ws_bytes", N, K, H), dev)
+        _lib.call("vcg_infonce_fwd", P(q), P(queue_km), P(lpos), N, K, H, float(inv_T), P(work), work.numel() * 4,
+                  P(lse), P(row_loss), P(omp0), P(loss), P(n_correct), s)
+        if want_logits:
+            buf, logits = infonce_logits_buffer(N, K, dev)
+            buf[:, 3].copy_(lpos)
+            _lib.call("vcg_infonce_logits", P(q), P(queue_km), N, K, H, float(inv_T), buf.data_ptr() + 16,
+                      buf.shape[1], s)
+        if want_dq:
+            dz = torch.empty((N, Kp), dtype=torch.bfloat16, device=dev)
+            _lib.call("vcg_infonce_dz", P(q), P(queue_km), P(lse), N, K, H, float(inv_T), float(scale), P(dz), Kp, s)
+            dq = torch.empty((N, H), dtype=torch.float32, device=dev)
+            gemm_splitk(dz, queue_km, dq, N, H, K, Kp, H, transA=False, transB=True, accumulate=False)
+    else:
+        buf, view = infonce_logits_buffer(N, K, dev)
+        rowdot(q, k, inv_T, out=buf[:, 3], ldo=buf.shape[1])
+        lpos = buf[:, 3].contiguous()
+        keyz = buf.data_ptr() + 16
+        _lib.call("vcg_gemm", F32, 0, 0, N, Kp, H, P(q), H, P(queue_km), H, keyz, buf.shape[1], None, ACT_NONE, None,
+                  buf.shape[1], None, float(inv_T), s)
+        work = ws(6 * N * 4, dev)
+        _lib.call("vcg_infonce_reduce_f32", keyz, buf.shape[1], P(lpos), N, K, P(work), work.numel() * 4, P(lse),
+                  P(row_loss), P(omp0), P(loss), P(n_correct), s)
+        if want_logits:
+            logits = view.clone() if want_dq else view  # (the gradient below overwrites the key columns)
+        if want_dq:
+            _lib.call("vcg_infonce_dz_f32", keyz, buf.shape[1], P(lse), float(scale), N, K, s)
+            dq = torch.empty((N, H), dtype=torch.float32, device=dev)
+            _lib.call("vcg_gemm", F32, 0, 1, N, H, Kp, keyz, buf.shape[1], P(queue_km), H, P(dq), H, None, ACT_NONE,
+                      None, H, None, 1.0, s)
+    if want_dq:
+        _lib.call("vcg_infonce_dq_pos", dt_code(q.dtype), P(dq), P(k), P(omp0), float(scale), N, H, s)
+    return lse, row_loss, loss, n_correct, dq, logits
+
+
 # ----------------------------------------------------------------------------- optimiser
 def sumsq(x, out, workspace=None):
     if workspace is None:

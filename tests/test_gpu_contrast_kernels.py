@@ -258,7 +258,7 @@ def test_outside_write_to_queue_is_seen():
 # ------------------------------------------------------------------------------------------------ InfoNCE
 NCE_CASES = [(1, 256, 256), (37, 1184, 768), (70, 1190, 768), (64, 65536, 768)]
 NCE_IDS = [f"N{n}-K{k}-H{h}" for n, k, h in NCE_CASES]
-NCE_SEED = {(1, 256, 256): 1, (37, 1184, 768): 1, (70, 1190, 768): 1, (64, 65536, 768): 1}
+NCE_SEED = {(1, 256, 256): 1, (37, 1184, 768): 1, (70, 1190, 768): 1, (64, 65536, 768): 1, (70, 200, 72): 1}
 
 
 @functools.lru_cache(maxsize=None)
@@ -391,6 +391,63 @@ def test_infonce_logits(N, K, H, prec):
     err = _rel(qa.grad.float(), c["dq"])
     print(f"logits-route dq rel err {err:.3e} (autocast {c['e_dq']:.3e})")
     assert err <= (1.5 * c["e_dq"] if prec == "bf16" else 1e-4)
+
+
+def test_infonce_k_tail():
+    """H = 72 is one 64-wide k stage plus one 8-wide chunk: the zero-filled k tail of the tile loop, which no H that is
+    a multiple of 64 reaches. 70 rows are a partial second row block, 200 keys a partial second tile. Only the InfoNCE
+    kernels run: the fp32 reduce gets its logits from the float64 reference instead of the GEMM. dZ elementwise against
+    float64: 2^-8 of the value for the bf16 rounding plus 1e-4 / (N T) for the fp32 exponentials and lse."""
+    from vcg_hip import _lib, ops
+    N, K, H = 70, 200, 72
+    c = _nce_case(N, K, H)
+    q, k, km = _nce_dev(c, torch.bfloat16)
+    s = ops.stream()
+
+    def fused(keep):
+        return ops.infonce(q[keep].contiguous(), k[keep].contiguous(), km, K, 1 / T)[:4]
+
+    def reduce_f32(keep):
+        z = c["z"][keep.cpu()].float().to(DEV)
+        n = z.shape[0]
+        buf, view = ops.infonce_logits_buffer(n, K, DEV)
+        view.copy_(z)
+        lse, row_loss, loss, n_correct = ops._nce_outputs(n, DEV)
+        lpos, work = z[:, 0].contiguous(), ops.ws(6 * n * 4, DEV)
+        _lib.call("vcg_infonce_reduce_f32", buf.data_ptr() + 16, buf.shape[1], lpos.data_ptr(), n, K, work.data_ptr(),
+                  work.numel() * 4, lse.data_ptr(), row_loss.data_ptr(), None, loss.data_ptr(), n_correct.data_ptr(), s)
+        return lse, row_loss, loss, n_correct
+
+    clear = c["clear"]
+    for name, run in (("bf16", fused), ("fp32", reduce_f32)):  # test_infonce_forward's assertions
+        lse, row_loss, loss, n_correct = run(torch.ones(N, dtype=torch.bool, device=DEV))
+        e_lse, e_row, e_loss = _maxerr(lse, c["lse"]), _maxerr(row_loss, c["row_loss"]), abs(loss.item() - c["loss"])
+        print(f"{name}: lse err {e_lse:.3e} row loss err {e_row:.3e} loss err {e_loss:.3e} "
+              f"n_correct {n_correct.item()} ref {int(c['correct'].sum())}")
+        assert e_lse <= 1e-4 and e_row <= 1e-4 and e_loss <= 1e-4
+        lse2, row2, loss2, n2 = run(torch.ones(N, dtype=torch.bool, device=DEV))
+        assert torch.equal(lse, lse2) and torch.equal(row_loss, row2) and torch.equal(loss, loss2)
+        assert torch.equal(n_correct, n2)
+        nc = run(clear.to(DEV))[3]
+        assert nc.item() == int(c["correct"][clear].sum())
+        assert 0 < nc.item() < int(clear.sum())
+
+    lse = fused(torch.ones(N, dtype=torch.bool, device=DEV))[0]
+    Kp = ops.queue_kp(K)
+    dZ = torch.empty((N, Kp), dtype=torch.bfloat16, device=DEV)
+    _lib.call("vcg_infonce_dz", q.data_ptr(), km.data_ptr(), lse.data_ptr(), N, K, H, 1 / T, 1 / (N * T), dZ.data_ptr(),
+              Kp, s)
+    want = torch.softmax(c["z"], 1)[:, 1:] / (N * T)
+    err = (dZ[:, :K].double().cpu() - want).abs()
+    bound = 2 ** -8 * want + 1e-4 / (N * T)
+    print(f"dZ max err {err.max().item():.3e}, worst err / bound {(err / bound).max().item():.3f}")
+    assert (err <= bound).all()
+
+    buf, view = ops.infonce_logits_buffer(N, K, DEV)
+    _lib.call("vcg_infonce_logits", q.data_ptr(), km.data_ptr(), N, K, H, 1 / T, buf.data_ptr() + 16, buf.shape[1], s)
+    e = _maxerr(view[:, 1:], c["z"][:, 1:])
+    print(f"key logits err {e:.3e}")
+    assert e <= 1e-3
 
 
 def test_infonce_shape_limits():

@@ -148,6 +148,42 @@ def test_mlm_f32_reduce_matches(R, V, H, kind):
     assert _rel(dz[:, :V].double().cpu() @ c["W"].double(), ref[0]) <= 1e-5
 
 
+def test_mlm_k_tail():
+    """H = 72 is one 64-wide k stage plus one 8-wide chunk: the zero-filled k tail of the tile loop, which no H that is
+    a multiple of 64 reaches. 70 rows are a partial second row block, 200 columns a partial second column tile. Only the
+    tile kernels run (no GEMM). dZ elementwise against float64: 2^-8 of the value for the bf16 rounding plus the
+    module's 1e-4 G / R for the fp32 exponentials and lse."""
+    from vcg_hip import ops
+    R, V, H = 70, 200, 72
+    c = _case(R, V, H, "rand")
+    X, W, rows, t = _dev(c)
+    lse, row_loss, loss, n_correct = ops.mlm_loss_fwd(X, rows, W, t)
+    e_lse = (lse.double().cpu() - c["lse"]).abs().max().item()
+    e_row = (row_loss.double().cpu() - c["row_loss"]).abs().max().item()
+    e_loss = abs(loss.item() - c["loss"])
+    print(f"lse err {e_lse:.3e} row loss err {e_row:.3e} loss err {e_loss:.3e} n_correct {n_correct.item()}")
+    assert e_lse <= 1e-4 and e_row <= 1e-4 and e_loss <= 1e-4
+    clear = c["clear"]
+    assert (~clear).float().mean().item() <= 0.02
+    keep = clear.to(DEV)
+    nc = ops.mlm_loss_fwd(X, rows[keep].contiguous(), W, t[keep].contiguous())[3]
+    assert nc.item() == int(c["correct"][clear].sum())
+
+    dZ = ops.mlm_loss_bwd(X, rows, W, t, lse, torch.full((), G, dtype=torch.float32, device=DEV))
+    z64 = c["X"].double()[c["rows"]] @ c["W"].double().t()
+    dz64 = (torch.softmax(z64, 1) - F.one_hot(c["t"], V).double()) * (G / R)
+    err = (dZ[:, :V].double().cpu() - dz64).abs()
+    bound = 2 ** -8 * dz64.abs() + 1e-4 * G / R
+    print(f"dZ max err {err.max().item():.3e}, worst err / bound {(err / bound).max().item():.3f}")
+    assert dZ.shape == (R, ops.mlm_vp(V)) and (err <= bound).all()
+
+    zl = ops.mlm_logits(X, W)  # every hidden row, the identity gather
+    assert zl.shape == (R + 13, ops.mlm_vp(V))
+    e_z = (zl[:, :V].double().cpu() - c["X"].double() @ c["W"].double().t()).abs().max().item()
+    print(f"logits err {e_z:.3e}")
+    assert e_z <= 1e-4
+
+
 @pytest.mark.parametrize("B,L,V,ld", [(3, 5, 1210, 1210), (3, 5, 1210, 1216), (2, 50, 30522, 30528)])
 def test_seq_softmax(B, L, V, ld):
     from vcg_hip import ops

@@ -12,32 +12,23 @@
 //                            `queue_km` [K][H] in the compute dtype, key-major: the operand of the tile kernel and of
 //                            the gradient GEMM. enqueue writes the N new keys into both at the DEVICE pointer and a
 //                            second one-thread launch advances it (no host round trip); rebuild is transpose + cast.
-//   infonce_tile_kernel      the fused InfoNCE: Z = q queue_km^T / T in 64 x 128 tiles, bf16 MFMA 16x16x32, fp32
-//                            accumulators -- the main loop of mlm_head.hip's mlm_tile_kernel, written again here so
-//                            that file stays as it is. LOSS keeps per-row online (max, sum, argmax) partials per split
-//                            of the key axis; DZ writes P / (N T) in bf16 for the gradient GEMM; LOGITS stores fp32.
-//                            The positive logit q . k / T (one per row, not a shared column) comes from rowdot_kernel
-//                            and joins in infonce_finalize_rows_kernel as column 0 (so it wins an exact tie).
+//   softmax_tile_kernel      the fused InfoNCE: Z = q queue_km^T / T by the row-softmax tile engine of softmax_tile.h
+//   <NcePolicy, .>           (shared with mlm_head.hip) under NcePolicy: no row gather, 1 / T applied to the
+//                            accumulators, no target column, key v is column 1 + v. LOSS keeps per-row online (max,
+//                            sum, argmax) partials per split of the key axis; DZ writes P / (N T) in bf16 for the
+//                            gradient GEMM; LOGITS stores fp32. The positive logit q . k / T (one per row, not a
+//                            shared column) comes from rowdot_kernel and joins in infonce_finalize_rows_kernel as
+//                            column 0 (so it wins an exact tie).
 //   fixed reduction trees, no atomics: bit-identical run to run.
 //
-// The fp32 parity mode forms the logits with vcg_gemm; infonce_rows_f32_kernel / infonce_dz_f32_kernel reduce them.
-#include "common.h"
-
-#include <math.h>
+// The fp32 parity mode forms the logits with vcg_gemm; softmax_rows_f32_kernel / infonce_dz_f32_kernel reduce them.
+#include "softmax_tile.h"
 
 namespace vcg {
 
 namespace {
 
-constexpr int NCE_BR = 64;           // rows per tile
-constexpr int NCE_BV = 128;          // keys per tile
-constexpr int NCE_BK = 64;           // k per stage
-constexpr int NCE_LD = NCE_BK + 8;   // LDS row stride in bf16 (144 B)
-constexpr int NCE_MAX_H = 4096;
-constexpr int NCE_TARGET_WGS = 512;  // workgroups wanted from row blocks x splits (256 CUs, two per CU)
 constexpr int SEL_MAX_C = 64;
-
-enum { NCE_LOSS = 0, NCE_DZ = 1, NCE_LOGITS = 2 };
 
 // ------------------------------------------------------------------------------------------------ momentum update
 // (contraction off for this expression: HIP's __fmul_rn / __fadd_rn are plain operators, which -ffp-contract=fast fuses)
@@ -213,251 +204,21 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ a, co
 }
 
 // ------------------------------------------------------------------------------------------------ InfoNCE
-struct NceArgs {
-  const bf16_t* X;  // q [N][H]
-  const bf16_t* W;  // queue_km [K][H]
-  int N, K, H, splits, tiles_per_split;
-  float inv_T;
-  float* part;       // NCE_LOSS: [4][splits][N] (max, sum, argmax value, argmax column bits; the column is 1 + key)
-  const float* lse;  // NCE_DZ
-  float scale;       // NCE_DZ: 1 / (N T)
-  void* out;         // NCE_DZ: bf16 [N][ldo]; NCE_LOGITS: fp32 [N][ldo], the pointer at the first key column
-  long long ldo;
-  int kp;            // K rounded up to 8: the columns K .. kp - 1 are written as zeros
+struct NcePolicy {
+  static constexpr bool GATHER = false, SCALED = true, TARGET = false;
+  static constexpr int COL0 = 1;  // column 0 is the positive logit, joined in infonce_finalize_rows_kernel
+  static __device__ __forceinline__ float dz_scale(const TileArgs& a) { return a.scale; }  // 1 / (N T)
+  static __device__ __forceinline__ float dz(float z, float lse, bool, float scale) { return __expf(z - lse) * scale; }
 };
 
-struct RowState {
-  float m, s, av;
-  int ai;
-};
-
-// a <- a merged with b over disjoint column sets; symmetric in (a, b) bit for bit (mlm_head.hip's state_merge)
-__device__ __forceinline__ void state_merge(RowState& a, const RowState& b) {
-  const float M = fmaxf(a.m, b.m);
-  if (M > -INFINITY) {
-    const float sa = a.m > -INFINITY ? a.s * expf(a.m - M) : 0.f;
-    const float sb = b.m > -INFINITY ? b.s * expf(b.m - M) : 0.f;
-    a.s = sa + sb;
-    a.m = M;
-  }
-  if (b.ai >= 0 && (a.ai < 0 || b.av > a.av || (b.av == a.av && b.ai < a.ai))) {
-    a.av = b.av;
-    a.ai = b.ai;
-  }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void infonce_tile_kernel(NceArgs a) {
-  __shared__ __attribute__((aligned(16))) bf16_t sX[NCE_BR * NCE_LD];
-  __shared__ __attribute__((aligned(16))) bf16_t sW[NCE_BV * NCE_LD];
-  __shared__ float sred[MODE == NCE_LOSS ? 16 * NCE_BR * 4 : 1];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, li = lane & 15;
-  const int r0 = blockIdx.x * NCE_BR;
-  const int ntv = (a.K + NCE_BV - 1) / NCE_BV;
-  const int vt0 = blockIdx.y * a.tiles_per_split;
-  const int vt1 = min(vt0 + a.tiles_per_split, ntv);
-  const int nk = (a.H + NCE_BK - 1) / NCE_BK;
-
-  // this thread's 16-B chunks of the X tile (2) and of the W tile (4): row = chunk / 8, k = 8 (chunk % 8)
-  const bf16_t* xp[2];
-  int xo[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = tid + j * 256, row = c >> 3;
-    xo[j] = row * NCE_LD + (c & 7) * 8;
-    const int r = r0 + row;
-    xp[j] = r < a.N ? a.X + (long long)r * a.H + (c & 7) * 8 : nullptr;
-  }
-
-  float lse[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + i * 16 + li;
-    lse[i] = 0.f;
-    if constexpr (MODE == NCE_DZ)
-      if (r < a.N) lse[i] = a.lse[r];
-  }
-
-  RowState st[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) st[i] = RowState{-INFINITY, 0.f, -INFINITY, -1};
-
-  for (int vt = vt0; vt < vt1; ++vt) {
-    const int v0 = vt * NCE_BV;
-    const bf16_t* wp[4];
-    int wo[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = tid + j * 256, row = c >> 3;
-      wo[j] = row * NCE_LD + (c & 7) * 8;
-      const int v = v0 + row;
-      wp[j] = v < a.K ? a.W + (long long)v * a.H + (c & 7) * 8 : nullptr;
-    }
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int f = 0; f < 2; ++f) acc[i][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    uint4 rx[2], rw[4];
-    auto fetch = [&](int k0) {
-      const int kc = k0 + (tid & 7) * 8;  // (H % 8 == 0: a chunk is inside the row or past it)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        rx[j] = (xp[j] && kc < a.H) ? *reinterpret_cast<const uint4*>(xp[j] + k0) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        rw[j] = (wp[j] && kc < a.H) ? *reinterpret_cast<const uint4*>(wp[j] + k0) : make_uint4(0, 0, 0, 0);
-    };
-    fetch(0);
-    for (int kt = 0; kt < nk; ++kt) {
-      __syncthreads();  // the previous stage's fragment reads are done
-#pragma unroll
-      for (int j = 0; j < 2; ++j) *reinterpret_cast<uint4*>(sX + xo[j]) = rx[j];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *reinterpret_cast<uint4*>(sW + wo[j]) = rw[j];
-      __syncthreads();
-      if (kt + 1 < nk) fetch((kt + 1) * NCE_BK);  // in flight during the MFMAs
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        s16x8 xf[4], wf[2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          xf[i] = *reinterpret_cast<const s16x8*>(sX + (i * 16 + li) * NCE_LD + s2 * 32 + g * 8);
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-          wf[f] = *reinterpret_cast<const s16x8*>(sW + (wave * 32 + f * 16 + li) * NCE_LD + s2 * 32 + g * 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int f = 0; f < 2; ++f)
-            acc[i][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[f], xf[i], acc[i][f], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int f = 0; f < 2; ++f) acc[i][f] *= a.inv_T;
-
-    // acc[i][f][r] = z(row r0 + 16 i + li, key v0 + 32 wave + 16 f + 4 g + r)
-    const int vb = v0 + wave * 32 + g * 4;
-    if constexpr (MODE == NCE_LOSS) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int v = vb + f * 16 + r;
-            if (v < a.K) {
-              const float z = acc[i][f][r];
-              tmax = fmaxf(tmax, z);
-              if (z > st[i].av || st[i].ai < 0) {  // (keys come in ascending order: the first maximum stays)
-                st[i].av = z;
-                st[i].ai = 1 + v;
-              }
-            }
-          }
-        if (tmax > -INFINITY) {
-          const float mn = fmaxf(st[i].m, tmax);
-          float s = st[i].m > -INFINITY ? st[i].s * __expf(st[i].m - mn) : 0.f;
-#pragma unroll
-          for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (vb + f * 16 + r < a.K) s += __expf(acc[i][f][r] - mn);
-          st[i].m = mn;
-          st[i].s = s;
-        }
-      }
-    } else if constexpr (MODE == NCE_DZ) {
-      bf16_t* dz = reinterpret_cast<bf16_t*>(a.out);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = r0 + i * 16 + li;
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          const int v4 = vb + f * 16;
-          if (row < a.N && v4 < a.kp) {  // (kp % 8 == 0, v4 % 4 == 0: the 4 columns are inside the padded row)
-            uint32_t w[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              bf16_t b2[2];
-#pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const int r = 2 * h + e, v = v4 + r;
-                b2[e] = f2bf(v < a.K ? __expf(acc[i][f][r] - lse[i]) * a.scale : 0.f);
-              }
-              w[h] = (uint32_t)b2[0] | ((uint32_t)b2[1] << 16);
-            }
-            *reinterpret_cast<uint2*>(dz + (long long)row * a.ldo + v4) = make_uint2(w[0], w[1]);
-          }
-        }
-      }
-    } else {
-      float* zo = reinterpret_cast<float*>(a.out);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = r0 + i * 16 + li;
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          const int v4 = vb + f * 16;
-          if (row < a.N && v4 < a.kp)  // (columns K .. kp - 1 are zeros: their W rows were zero-filled)
-            *reinterpret_cast<float4*>(zo + (long long)row * a.ldo + v4) =
-                make_float4(acc[i][f][0], acc[i][f][1], acc[i][f][2], acc[i][f][3]);
-        }
-      }
-    }
-  }
-
-  if constexpr (MODE == NCE_LOSS) {
-    // the 16 states of a row (4 waves x 4 lane groups), merged in that order by one thread per row
-    const int src = wave * 4 + g;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float* d = sred + (src * NCE_BR + i * 16 + li) * 4;
-      d[0] = st[i].m;
-      d[1] = st[i].s;
-      d[2] = st[i].av;
-      d[3] = __int_as_float(st[i].ai);
-    }
-    __syncthreads();
-    if (tid < NCE_BR && r0 + tid < a.N) {
-      RowState t{-INFINITY, 0.f, -INFINITY, -1};
-      for (int q = 0; q < 16; ++q) {
-        const float* d = sred + (q * NCE_BR + tid) * 4;
-        state_merge(t, RowState{d[0], d[1], d[2], __float_as_int(d[3])});
-      }
-      const long long SR = (long long)a.splits * a.N, o = (long long)blockIdx.y * a.N + r0 + tid;
-      a.part[o] = t.m;
-      a.part[SR + o] = t.s;
-      a.part[2 * SR + o] = t.av;
-      a.part[3 * SR + o] = __int_as_float(t.ai);
-    }
-  }
-}
-
-// One wave per row: lane l merges splits l, l + 64, ... in order, a butterfly over the lanes (state_merge is symmetric),
-// then the positive logit as column 0. rowres [2][N]: the row's loss and whether its argmax is column 0.
+// One wave per row: the splits merged, then the positive logit as column 0. rowres [2][N]: the row's loss and whether
+// its argmax is column 0.
 __global__ __launch_bounds__(256) void infonce_finalize_rows_kernel(const float* part, int splits, int N,
                                                                     const float* lpos, float* lse, float* row_loss,
                                                                     float* omp0, float* rowres) {
   const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= N) return;
-  const long long SR = (long long)splits * N;
-  RowState t{-INFINITY, 0.f, -INFINITY, -1};
-  for (int s = lane; s < splits; s += 64) {
-    const long long o = (long long)s * N + r;
-    state_merge(t, RowState{part[o], part[SR + o], part[2 * SR + o], __float_as_int(part[3 * SR + o])});
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    RowState u{__shfl_xor(t.m, o, 64), __shfl_xor(t.s, o, 64), __shfl_xor(t.av, o, 64), __shfl_xor(t.ai, o, 64)};
-    state_merge(t, u);
-  }
+  RowState<false> t = merge_splits<false>(part, splits, N, r, lane);
   if (lane == 0) {
     const float zp = lpos[r];
     if (omp0) {
@@ -467,83 +228,14 @@ __global__ __launch_bounds__(256) void infonce_finalize_rows_kernel(const float*
       const float sn = t.m > -INFINITY ? t.s * expf(t.m - M) : 0.f;
       omp0[r] = sn / (sn + expf(zp - M));
     }
-    state_merge(t, RowState{zp, 1.f, zp, 0});
+    RowState<false> pos;
+    pos.m = zp; pos.s = 1.f; pos.av = zp; pos.ai = 0;
+    state_merge(t, pos);
     const float l = t.m + logf(t.s), rl = l - zp;
     if (lse) lse[r] = l;
     if (row_loss) row_loss[r] = rl;
     rowres[r] = rl;
     rowres[N + r] = t.ai == 0 ? 1.f : 0.f;
-  }
-}
-
-__global__ __launch_bounds__(256) void infonce_mean_kernel(const float* rowres, int N, float* mean_loss,
-                                                           long long* n_correct) {
-  __shared__ double ssum[256];
-  __shared__ int scnt[256];
-  const int tid = threadIdx.x;
-  double lsum = 0.0;
-  int cnt = 0;
-  for (int r = tid; r < N; r += 256) {
-    lsum += (double)rowres[r];
-    cnt += rowres[N + r] != 0.f ? 1 : 0;
-  }
-  ssum[tid] = lsum;
-  scnt[tid] = cnt;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      ssum[tid] += ssum[tid + o];
-      scnt[tid] += scnt[tid + o];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (mean_loss) mean_loss[0] = (float)(ssum[0] / (double)N);
-    if (n_correct) n_correct[0] = scnt[0];
-  }
-}
-
-// fp32 key logits z [N][ldz] (already divided by T) -> the partials of one split (one workgroup per row)
-__global__ __launch_bounds__(256) void infonce_rows_f32_kernel(const float* z, long long ldz, int N, int K,
-                                                               float* part) {
-  __shared__ float sred[256 * 4];
-  const int r = blockIdx.x, tid = threadIdx.x;
-  const float* zr = z + (long long)r * ldz;
-  RowState t{-INFINITY, 0.f, -INFINITY, -1};
-  for (int v = tid; v < K; v += 256) {
-    const float x = zr[v];
-    if (x > t.av || t.ai < 0) {
-      t.av = x;
-      t.ai = 1 + v;
-    }
-    const float mn = fmaxf(t.m, x);
-    t.s = (t.m > -INFINITY ? t.s * expf(t.m - mn) : 0.f) + expf(x - mn);
-    t.m = mn;
-  }
-  float* d = sred + tid * 4;
-  d[0] = t.m;
-  d[1] = t.s;
-  d[2] = t.av;
-  d[3] = __int_as_float(t.ai);
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {  // fixed tree
-    if (tid < o) {
-      float* p = sred + tid * 4;
-      const float* q = sred + (tid + o) * 4;
-      RowState x{p[0], p[1], p[2], __float_as_int(p[3])};
-      state_merge(x, RowState{q[0], q[1], q[2], __float_as_int(q[3])});
-      p[0] = x.m;
-      p[1] = x.s;
-      p[2] = x.av;
-      p[3] = __int_as_float(x.ai);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    part[r] = sred[0];
-    part[(long long)N + r] = sred[1];
-    part[2LL * N + r] = sred[2];
-    part[3LL * N + r] = sred[3];
   }
 }
 
@@ -567,46 +259,17 @@ __global__ __launch_bounds__(256) void infonce_dq_pos_kernel(float* dq, const T*
   dq[i] -= omp0[n] * scale * to_f<T>(k[i]);
 }
 
-// splits of the key axis for N rows: a pure function of the shape (the reduction order follows it)
-void nce_split(int N, int K, int* splits, int* tps) {
-  const int ntv = (K + NCE_BV - 1) / NCE_BV, nrb = (N + NCE_BR - 1) / NCE_BR;
-  int s = (NCE_TARGET_WGS + nrb - 1) / nrb;
-  s = s < 1 ? 1 : (s > ntv ? ntv : s);
-  *tps = (ntv + s - 1) / s;
-  *splits = (ntv + *tps - 1) / *tps;
-}
-
-// workspace: 4 floats per (split, row), then 2 per row (rowres)
-long long nce_ws_floats(int splits, int N) { return (4LL * splits + 2) * N; }
-
-int nce_shape_ok(int N, int K, int H) {
-  if (N <= 0 || K <= 0 || H <= 0) {
-    set_error("infonce: empty shape");
-    return VCG_ERR_INVALID;
-  }
-  if (H % 8 != 0 || H > NCE_MAX_H) {
-    set_error("infonce: H must be a multiple of 8, at most 4096");
-    return VCG_ERR_UNSUPPORTED;
-  }
-  return VCG_OK;
-}
-
 void nce_finalize(float* ws, int splits, int N, const float* lpos, float* lse, float* row_loss, float* omp0,
                   float* mean_loss, long long* n_correct, hipStream_t stream) {
   float* rowres = ws + 4LL * splits * N;
   hipLaunchKernelGGL(infonce_finalize_rows_kernel, dim3((N + 3) / 4), dim3(256), 0, stream, ws, splits, N, lpos, lse,
                      row_loss, omp0, rowres);
-  hipLaunchKernelGGL(infonce_mean_kernel, dim3(1), dim3(256), 0, stream, rowres, N, mean_loss, n_correct);
+  hipLaunchKernelGGL(softmax_mean_kernel, dim3(1), dim3(256), 0, stream, rowres, N, mean_loss, n_correct);
 }
 
-NceArgs nce_args(const void* q, const void* km, int N, int K, int H, float inv_T) {
-  NceArgs a{};
-  a.X = reinterpret_cast<const bf16_t*>(q);
-  a.W = reinterpret_cast<const bf16_t*>(km);
-  a.N = N; a.K = K; a.H = H;
-  a.inv_T = inv_T;
-  a.kp = (K + 7) / 8 * 8;
-  nce_split(N, K, &a.splits, &a.tiles_per_split);
+TileArgs nce_args(const void* q, const void* km, int N, int K, int H, float inv_T) {
+  TileArgs a = tile_args(q, km, N, K, H);
+  a.zscale = inv_T;
   return a;
 }
 
@@ -721,20 +384,20 @@ VCG_API long long vcg_infonce_ws_bytes(int N, int K, int H) {
   (void)H;
   if (N <= 0 || K <= 0) return 0;
   int splits, tps;
-  nce_split(N, K, &splits, &tps);
-  return nce_ws_floats(splits, N) * 4;
+  tile_split(N, K, &splits, &tps);
+  return tile_ws_floats<NcePolicy>(splits, N) * 4;
 }
 
 VCG_API int vcg_infonce_fwd(const void* q, const void* queue_km, const float* lpos, int N, int K, int H, float inv_T,
                             float* ws, long long ws_bytes, float* lse, float* row_loss, float* one_minus_p0,
                             float* mean_loss, long long* n_correct, hipStream_t stream) {
-  if (int rc = nce_shape_ok(N, K, H)) return rc;
+  if (int rc = tile_shape_ok("infonce", N, K, H)) return rc;
   VCG_REQUIRE(q && queue_km && lpos && ws, "null argument");
   VCG_REQUIRE((((uintptr_t)q | (uintptr_t)queue_km) & 15) == 0, "q and queue_km must be 16-B aligned");
   VCG_REQUIRE(ws_bytes >= vcg_infonce_ws_bytes(N, K, H), "workspace too small");
-  NceArgs a = nce_args(q, queue_km, N, K, H, inv_T);
+  TileArgs a = nce_args(q, queue_km, N, K, H, inv_T);
   a.part = ws;
-  hipLaunchKernelGGL(infonce_tile_kernel<NCE_LOSS>, dim3((N + NCE_BR - 1) / NCE_BR, a.splits), dim3(256), 0, stream, a);
+  tile_launch<NcePolicy, TILE_LOSS>(a, stream);
   nce_finalize(ws, a.splits, N, lpos, lse, row_loss, one_minus_p0, mean_loss, n_correct, stream);
   VCG_LAUNCH_CHECK();
   return VCG_OK;
@@ -742,31 +405,30 @@ VCG_API int vcg_infonce_fwd(const void* q, const void* queue_km, const float* lp
 
 VCG_API int vcg_infonce_dz(const void* q, const void* queue_km, const float* lse, int N, int K, int H, float inv_T,
                            float scale, void* dZ, long long ldz, hipStream_t stream) {
-  if (int rc = nce_shape_ok(N, K, H)) return rc;
+  if (int rc = tile_shape_ok("infonce", N, K, H)) return rc;
   VCG_REQUIRE(q && queue_km && lse && dZ, "null argument");
   VCG_REQUIRE((((uintptr_t)q | (uintptr_t)queue_km | (uintptr_t)dZ) & 15) == 0, "q, queue_km and dZ must be 16-B aligned");
   VCG_REQUIRE(ldz == ((long long)K + 7) / 8 * 8, "ldz must be K rounded up to a multiple of 8");
-  NceArgs a = nce_args(q, queue_km, N, K, H, inv_T);
+  TileArgs a = nce_args(q, queue_km, N, K, H, inv_T);
   a.lse = lse;
   a.scale = scale;
   a.out = dZ;
   a.ldo = ldz;
-  hipLaunchKernelGGL(infonce_tile_kernel<NCE_DZ>, dim3((N + NCE_BR - 1) / NCE_BR, a.splits), dim3(256), 0, stream, a);
+  tile_launch<NcePolicy, TILE_DZ>(a, stream);
   VCG_LAUNCH_CHECK();
   return VCG_OK;
 }
 
 VCG_API int vcg_infonce_logits(const void* q, const void* queue_km, int N, int K, int H, float inv_T, float* key_logits,
                                long long ldz, hipStream_t stream) {
-  if (int rc = nce_shape_ok(N, K, H)) return rc;
+  if (int rc = tile_shape_ok("infonce", N, K, H)) return rc;
   VCG_REQUIRE(q && queue_km && key_logits, "null argument");
   VCG_REQUIRE((((uintptr_t)q | (uintptr_t)queue_km | (uintptr_t)key_logits) & 15) == 0, "16-B alignment");
   VCG_REQUIRE(ldz % 4 == 0 && ldz >= ((long long)K + 7) / 8 * 8, "ldz: a multiple of 4, at least K rounded up to 8");
-  NceArgs a = nce_args(q, queue_km, N, K, H, inv_T);
+  TileArgs a = nce_args(q, queue_km, N, K, H, inv_T);
   a.out = key_logits;
   a.ldo = ldz;
-  hipLaunchKernelGGL(infonce_tile_kernel<NCE_LOGITS>, dim3((N + NCE_BR - 1) / NCE_BR, a.splits), dim3(256), 0, stream,
-                     a);
+  tile_launch<NcePolicy, TILE_LOGITS>(a, stream);
   VCG_LAUNCH_CHECK();
   return VCG_OK;
 }
@@ -776,8 +438,9 @@ VCG_API int vcg_infonce_reduce_f32(const float* key_logits, long long ldz, const
                                    float* mean_loss, long long* n_correct, hipStream_t stream) {
   VCG_REQUIRE(key_logits && lpos && ws, "null argument");
   VCG_REQUIRE(N > 0 && K > 0 && ldz >= K, "bad shape");
-  VCG_REQUIRE(ws_bytes >= nce_ws_floats(1, N) * 4, "workspace too small");
-  hipLaunchKernelGGL(infonce_rows_f32_kernel, dim3(N), dim3(256), 0, stream, key_logits, ldz, N, K, ws);
+  VCG_REQUIRE(ws_bytes >= tile_ws_floats<NcePolicy>(1, N) * 4, "workspace too small");
+  hipLaunchKernelGGL(softmax_rows_f32_kernel<NcePolicy>, dim3(N), dim3(256), 0, stream, key_logits, ldz, nullptr, N, K,
+                     ws);
   nce_finalize(ws, 1, N, lpos, lse, row_loss, one_minus_p0, mean_loss, n_correct, stream);
   VCG_LAUNCH_CHECK();
   return VCG_OK;

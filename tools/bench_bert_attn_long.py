@@ -1,5 +1,7 @@
 """BERT attention forward + backward alone, fused (bert_attn.hip / bert_attn_long.hip) vs unfused (QK^T GEMM -> softmax ->
-PV GEMM), B = 64, 12 heads, p = 0.1, L = 128 .. 512 (device events over 20 calls; profiles/long_text_attn_ab.txt)."""
+PV GEMM), B = 64, 12 heads, p = 0.1, L = 128 .. 512 (device events over 20 calls; profiles/long_text_attn_ab.txt). With
+VCG_LIB_PATH it times another build of the library: the fused lines of the parent's and this tree's are compared in
+profiles/bert_attn_shared_ab.txt."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "video-chapter-generation_amd"))
 import torch

@@ -1,5 +1,6 @@
 // Fused BERT self-attention for the bf16 train / scoring path: one workgroup per (sequence, head), L <= 128 keys
-// (128 < L <= 512: the tiled kernels of bert_attn_long.hip, dispatched by the entry points below), head dim 64, HF BertModel eager-attention semantics (model/lang/bert_hugface.py:20 via two_stream.py:172-179):
+// (128 < L <= 512: the tiled kernels of bert_attn_long.hip, dispatched by the entry points below), head dim 64, HF
+// BertModel eager-attention semantics (model/lang/bert_hugface.py:20 via two_stream.py:172-179):
 //
 //   forward : S = Q K^T, P = softmax(scale * S + mask_add) (a row with no valid key is uniform over the L keys, as
 //             HF's finfo.min bias gives), Pd = dropout(P), ctx = Pd V; saved: (row max, 1 / row sum) per query
@@ -12,11 +13,12 @@
 // forward reads Q, K, V once and writes ctx; the backward reads Q, K, V, dO, O once and writes dQ, dK, dV.
 // Dropout regenerates the unfused kernels' mask exactly (same counter-hash index (z * L + q) * Lp + key).
 //
-// MFMA: mfma_f32_16x16x32_bf16 (lane l = 16 g + i holds A[row i][k-set g], B[k-set g][col i], D[rows 4g..4g+3]
-// [col i]). A k-step's 32 k indices only have to be the same SET on both operands, so a D fragment (4 consecutive
-// rows per lane) feeds the next MFMA's operand straight from registers: rows {32s + 4g + r, 32s + 16 + 4g + r} of
-// two adjacent D tiles form lane group g's k-set of k-step s. Only dS crosses waves (through LDS) in the backward.
-#include "bert_attn_tiles.h"
+// The kernels are built from the steps of bert_attn_steps.h (workgroup coordinates, tile and fragment loads, score
+// tiles, the recomputed probability, dropout to fragment, the PV and dV / dK accumulations, the row store), which the
+// tiled kernels share; the MFMA fragment layout is described there. What is written out here is this algorithm's own:
+// the whole-row softmax (normalise, then dropout), D through LDS, and dQ from the LDS copy of dS -- only dS crosses
+// waves in the backward.
+#include "bert_attn_host.h"
 
 using namespace vcg;
 using namespace vcg::attn;
@@ -34,55 +36,22 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
   __shared__ __attribute__((aligned(16))) bf16_t Ks[LT * DH];
   __shared__ __attribute__((aligned(16))) bf16_t Vt[DH * TP];
   __shared__ uint8_t kval[LT];
-  const int z = blockIdx.x, b = z / nh, h = z - b * nh;
-  const int H = nh * DH;
-  const long long ld = 3LL * H;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, i = lane & 15;
-  // sequence b: rows row0 .. row0 + L - 1 (packed: seq[b] .. seq[b + 1] - 1; else b Lmax .. + Lmax - 1)
-  const int row0 = seq ? seq[b] : b * Lmax;
-  const int L = seq ? seq[b + 1] - row0 : Lmax;
-  const bf16_t* base = qkv + (long long)row0 * ld + h * DH;  // Q of (b, h); K at + H, V at + 2 H
+  const Head hd(nh, 1, seq, Lmax, Lp);
+  const int L = hd.L, H = hd.H, tid = hd.tid, w = hd.w, g = hd.g, i = hd.i;
+  const bf16_t* base = qkv + hd.qo;  // Q of (b, h); K at + H, V at + 2 H
 
-  for (int c = tid; c < LT * 8; c += 256) {
-    const int r = c >> 3, ch = c & 7;
-    *reinterpret_cast<uint4*>(Ks + r * DH + 8 * swz(r, ch)) = ld16(base + r * ld + H + 8 * ch, r < L);
-  }
-  load_transpose(base + 2 * H, ld, L, Vt, nullptr, tid);
-  if (tid < LT) kval[tid] = tid < L && (mask == nullptr || mask[(long long)row0 + tid] != 0);
+  load_rm(base + H, hd.ld, L, Ks, tid);
+  load_transpose(base + 2 * H, hd.ld, L, Vt, nullptr, tid);
+  load_key_flags(kval, mask, hd.row0, L, tid);
   s16x8 qf[2][2];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int q = 32 * w + 16 * qt + i;
-      const uint4 u = ld16(base + (long long)q * ld + 8 * (4 * s + g), q < L);
-      qf[qt][s] = __builtin_bit_cast(s16x8, u);
-    }
+  load_frags(qf, base, hd.ld, 32 * w, L, g, i);
   __syncthreads();
   // (a packed sequence shorter than 128 rows: tiles of keys / queries past its end add nothing and are skipped)
   if (32 * w >= L) return;  // every query of this wave is past the end (no barrier follows)
 
-  f32x4 sacc[2][8];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int kt = 0; kt < 8; ++kt) sacc[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int kt = 0; kt < 8; ++kt)
-    if (16 * kt < L) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const s16x8 kf = frag_rm(Ks, 16 * kt + i, 4 * s + g);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) sacc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][s], sacc[qt][kt], 0, 0, 0);
-      }
-    }
-  // lane holds S^T[key 16 kt + 4 g + r][query 32 w + 16 qt + i]
-  uint32_t vb = 0;  // bit 4 kt + r: key 16 kt + 4 g + r is valid
-#pragma unroll
-  for (int kt = 0; kt < 8; ++kt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) vb |= kval[16 * kt + 4 * g + r] ? (1u << (4 * kt + r)) : 0u;
+  f32x4 sacc[2][8];  // lane holds S^T[key 16 kt + 4 g + r][query 32 w + 16 qt + i]
+  key_tiles<8>(sacc, Ks, 0, L, qf, g, i);
+  const uint32_t vb = key_bits<8>(kval, 0, g);
   const float rs = p > 0.f ? 1.f / (1.f - p) : 1.f;
   s16x8 pf[2][4];
 #pragma unroll
@@ -114,48 +83,20 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.f / sum;
-    if (g == 0 && q < L) stats[(long long)z * LT + q] = make_float2(mx, inv);
-    const uint64_t rowi = ((uint64_t)z * Lmax + q) * (uint64_t)Lp;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float a[4], c[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k0 = 32 * s + 4 * g + r, k1 = k0 + 16;
-        const float p0 = sacc[qt][2 * s][r] * inv, p1 = sacc[qt][2 * s + 1][r] * inv;
-        a[r] = (q < L && dropout_keep(seed, rowi + k0, p)) ? p0 * rs : 0.f;
-        c[r] = (q < L && dropout_keep(seed, rowi + k1, p)) ? p1 * rs : 0.f;
-      }
-      pf[qt][s] = pack8(a, c);
-    }
+    if (g == 0 && q < L) stats[hd.so + q] = make_float2(mx, inv);
+    dropout_frags(pf[qt], sacc[qt], q < L, hd.drop_row(q), inv, rs, p, seed, g);
   }
 
-  f32x4 oacc[4][2];
+  f32x4 oacc[4][2];  // lane holds O^T[d 16 dt + 4 g + r][query 32 w + 16 qt + i]
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) oacc[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    if (32 * s < L) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const s16x8 vf = frag_split(Vt, 16 * dt + i, 32 * s + 4 * g);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) oacc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt][s], oacc[dt][qt], 0, 0, 0);
-      }
-    }
-  // lane holds O^T[d 16 dt + 4 g + r][query 32 w + 16 qt + i]
+  pv_step(oacc, Vt, pf, L, g, i);
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = 32 * w + 16 * qt + i;
-    if (q < L) {
-      bf16_t* o = ctx + ((long long)row0 + q) * H + h * DH + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        *reinterpret_cast<uint2*>(o + 16 * dt) =
-            make_uint2(pack2(oacc[dt][qt][0], oacc[dt][qt][1]), pack2(oacc[dt][qt][2], oacc[dt][qt][3]));
-    }
+    if (q < L) store_row64(ctx + hd.co + (long long)q * H + 4 * g, oacc, qt);
   }
 }
 
@@ -179,57 +120,29 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
   __shared__ float2 st[LT];
   __shared__ float Dp[4 * LT];  // per-wave partial rowsum(dP o P) over the wave's 32 keys
   __shared__ uint8_t kval[LT];
-  const int z = blockIdx.x, b = z / nh, h = z - b * nh;
-  const int H = nh * DH;
-  const long long ld = 3LL * H;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, i = lane & 15;
-  const int row0 = seq ? seq[b] : b * Lmax;
-  const int L = seq ? seq[b + 1] - row0 : Lmax;
-  const bf16_t* base = qkv + (long long)row0 * ld + h * DH;
-  const bf16_t* dob = dctx + (long long)row0 * H + h * DH;
-  bf16_t* gq = dqkv + (long long)row0 * ld + h * DH;
+  const Head hd(nh, 1, seq, Lmax, Lp);
+  const int L = hd.L, H = hd.H, tid = hd.tid, w = hd.w, g = hd.g, i = hd.i;
+  const long long ld = hd.ld;
+  const bf16_t* base = qkv + hd.qo;
+  const bf16_t* dob = dctx + hd.co;
+  bf16_t* gq = dqkv + hd.qo;
 
   load_transpose(base, ld, L, Qt, Qs, tid);
   load_transpose(dob, H, L, dOt, dOs, tid);
   load_transpose(base + H, ld, L, Kt, nullptr, tid);
-  if (tid < LT) {
-    kval[tid] = tid < L && (mask == nullptr || mask[(long long)row0 + tid] != 0);
-    st[tid] = tid < L ? stats[(long long)z * LT + tid] : make_float2(0.f, 0.f);
-  }
+  load_key_flags(kval, mask, hd.row0, L, tid);
+  if (tid < LT) st[tid] = tid < L ? stats[hd.so + tid] : make_float2(0.f, 0.f);
   s16x8 kf[2][2], vf[2][2];
-#pragma unroll
-  for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int key = 32 * w + 16 * kt + i;
-      kf[kt][s] = __builtin_bit_cast(s16x8, ld16(base + (long long)key * ld + H + 8 * (4 * s + g), key < L));
-      vf[kt][s] = __builtin_bit_cast(s16x8, ld16(base + (long long)key * ld + 2 * H + 8 * (4 * s + g), key < L));
-    }
+  load_frags(kf, base + H, ld, 32 * w, L, g, i);
+  load_frags(vf, base + 2 * H, ld, 32 * w, L, g, i);
   __syncthreads();
 
-  f32x4 sacc[8][2], pacc[8][2];
-#pragma unroll
-  for (int qt = 0; qt < 8; ++qt)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) sacc[qt][kt] = pacc[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
   // (tiles past the end of a packed sequence add nothing: skipped; a wave whose 32 keys are all past it keeps zeros,
   // so its dS entries -- read by every wave's dQ -- are exact zeros)
   const bool wkeys = 32 * w < L;
-#pragma unroll
-  for (int qt = 0; qt < 8; ++qt)
-    if (wkeys && 16 * qt < L) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const s16x8 qa = frag_rm(Qs, 16 * qt + i, 4 * s + g);
-        const s16x8 da = frag_rm(dOs, 16 * qt + i, 4 * s + g);
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          sacc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[kt][s], sacc[qt][kt], 0, 0, 0);
-          pacc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[kt][s], pacc[qt][kt], 0, 0, 0);
-        }
-      }
-    }
-  // lane holds S / dPd [query 16 qt + 4 g + r][key 32 w + 16 kt + i]
+  f32x4 sacc[8][2], pacc[8][2];  // lane holds S / dPd [query 16 qt + 4 g + r][key 32 w + 16 kt + i]
+  query_tiles<8>(sacc, Qs, 0, wkeys ? L : 0, kf, g, i);
+  query_tiles<8>(pacc, dOs, 0, wkeys ? L : 0, vf, g, i);
   const float rs = p > 0.f ? 1.f / (1.f - p) : 1.f;
   bool kv[2];
   int keyi[2];
@@ -245,16 +158,12 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
     for (int r = 0; r < 4; ++r) {
       const int q = 16 * qt + 4 * g + r;
       const float2 mi = st[q];
-      const uint64_t rowi = ((uint64_t)z * Lmax + q) * (uint64_t)Lp;
+      const uint64_t rowi = hd.drop_row(q);
       float part = 0.f;
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         const int key = keyi[kt];
-        float P = 0.f;
-        if (q < L) {
-          if (mi.x == -INFINITY) P = key < L ? mi.y : 0.f;
-          else P = kv[kt] ? __expf(sacc[qt][kt][r] * scale - mi.x) * mi.y : 0.f;
-        }
+        const float P = attn_prob(sacc[qt][kt][r], scale, mi, kv[kt], key < L, q < L);
         const bool keep = q < L && key < L && dropout_keep(seed, rowi + key, p);
         const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
         keepb |= keep ? (1ull << (8 * qt + 2 * r + kt)) : 0ull;
@@ -286,52 +195,22 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
     }
 
   // dV^T = dO^T Pd, dK^T = Q^T dS over the 128 queries (k-step s: queries {32 s + 4 g + r, 32 s + 16 + 4 g + r})
-  f32x4 dv[4][2], dk[4][2];
+  f32x4 dv[4][2], dk[4][2];  // lane holds dV^T / dK^T [d 16 dt + 4 g + r][key 32 w + 16 kt + i]
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    if (!wkeys || 32 * s >= L) continue;
-    s16x8 pb[2], sb[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      float a[4], c[4], e[4], f[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        a[r] = sacc[2 * s][kt][r];
-        c[r] = sacc[2 * s + 1][kt][r];
-        e[r] = pacc[2 * s][kt][r];
-        f[r] = pacc[2 * s + 1][kt][r];
-      }
-      pb[kt] = pack8(a, c);
-      sb[kt] = pack8(e, f);
-    }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const s16x8 oa = frag_split(dOt, 16 * dt + i, 32 * s + 4 * g);
-      const s16x8 qa = frag_split(Qt, 16 * dt + i, 32 * s + 4 * g);
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        dv[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa, pb[kt], dv[dt][kt], 0, 0, 0);
-        dk[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, sb[kt], dk[dt][kt], 0, 0, 0);
-      }
-    }
-  }
-  // lane holds dV^T / dK^T [d 16 dt + 4 g + r][key 32 w + 16 kt + i]
+  for (int s = 0; s < 4; ++s)
+    if (wkeys && 32 * s < L)
+      dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], dOt, Qt, 32 * s, g, i);
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     const int key = keyi[kt];
     if (key < L) {
       bf16_t* o = gq + (long long)key * ld + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        *reinterpret_cast<uint2*>(o + H + 16 * dt) =
-            make_uint2(pack2(dk[dt][kt][0], dk[dt][kt][1]), pack2(dk[dt][kt][2], dk[dt][kt][3]));
-        *reinterpret_cast<uint2*>(o + 2 * H + 16 * dt) =
-            make_uint2(pack2(dv[dt][kt][0], dv[dt][kt][1]), pack2(dv[dt][kt][2], dv[dt][kt][3]));
-      }
+      store_row64(o + H, dk, kt);
+      store_row64(o + 2 * H, dv, kt);
     }
   }
   __syncthreads();  // dSm complete
@@ -359,27 +238,15 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = 32 * w + 16 * qt + i;
-    if (q < L) {
-      bf16_t* o = gq + (long long)q * ld + 4 * g;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        *reinterpret_cast<uint2*>(o + 16 * dt) =
-            make_uint2(pack2(dq[dt][qt][0], dq[dt][qt][1]), pack2(dq[dt][qt][2], dq[dt][qt][3]));
-    }
+    if (q < L) store_row64(gq + (long long)q * ld + 4 * g, dq, qt);
   }
 }
 
-}  // namespace
-
-VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
-                                     int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
-                                     unsigned long long seed, hipStream_t s);
-VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq,
-                                     const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale,
-                                     float dropout_p, unsigned long long seed, hipStream_t s);
-
-static int attn_check(const char* fn, const void* qkv, const void* out, const void* stats, int B, int nh, int L, int Lp) {
-  if (!qkv || !out || !stats || B < 0 || nh <= 0 || L < 0 || Lp < L) {
+// The one argument check of the four entry points (io: ctx / dqkv). *nT: the 128-row tiles of the stats rows, and
+// the tiled kernels' grid is one workgroup per (sequence, head, tile)
+int attn_check(const char* fn, const void* qkv, const void* io, const void* stats, int B, int nh, int L, int Lp,
+               int* nT) {
+  if (!qkv || !io || !stats || B < 0 || nh <= 0 || L < 0 || Lp < L) {
     set_error(std::string(fn) + ": invalid arguments");
     return VCG_ERR_INVALID;
   }
@@ -387,43 +254,44 @@ static int attn_check(const char* fn, const void* qkv, const void* out, const vo
     set_error(std::string(fn) + ": L > 512 is not supported by the fused kernels");
     return VCG_ERR_UNSUPPORTED;
   }
+  *nT = stats_tiles(L);
+  if ((long long)B * nh * *nT > 0x7fffffffLL) {  // (more workgroups than a grid holds)
+    set_error(std::string(fn) + ": the tiled kernels take 128 < L <= 512");
+    return VCG_ERR_UNSUPPORTED;
+  }
   return VCG_OK;
 }
 
-// float2 [B * nh][128] (row max, 1 / row sum) at L <= 128; above it the tiled kernels' layout (bert_attn_tiles.h):
-// the row statistics and the backward's D over the sequence length rounded up to the 128-row tile
+}  // namespace
+
+// (the layout: bert_attn_host.h)
 VCG_API long long vcg_bert_attn_stats_bytes(int B, int nh, int L) {
   if (B < 0 || nh < 0 || L < 0) return 0;
-  const long long Lr = L <= LT ? LT : (L + LT - 1) / LT * LT;
-  return (long long)B * nh * Lr * (long long)(L <= LT ? sizeof(float2) : sizeof(float2) + sizeof(float));
-}
-
-VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx, void* stats, int B, int nh, int L,
-                              int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
-  return vcg_bert_attn_fwd_varlen(qkv, mask, nullptr, ctx, stats, B, nh, L, Lp, scale, dropout_p, seed, s);
+  return stats_rows(B, nh, L) * (long long)(L <= LT ? sizeof(float2) : sizeof(float2) + sizeof(float));
 }
 
 // Packed (unpadded) sequences: sequence b's rows are seq[b] .. seq[b + 1] - 1 of qkv / ctx (at most Lmax <= 512 of
-// them; Lmax > 128: the tiled kernels of bert_attn_long.hip), mask the key flags of those rows (NULL: every row is a key); stats and the dropout counters keep the padded
-// [B][nh][Lmax] index space, so a sequence whose kept rows are a prefix of its padded rows gets the padded result.
+// them; Lmax > 128: the tiled kernels of bert_attn_long.hip), mask the key flags of those rows (NULL: every row is a
+// key); stats and the dropout counters keep the padded [B][nh][Lmax] index space, so a sequence whose kept rows are a
+// prefix of its padded rows gets the padded result. seq NULL: padded, sequence b at rows b Lmax .. b Lmax + Lmax - 1.
 VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
                                      int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
                                      unsigned long long seed, hipStream_t s) {
   if (B == 0 || Lmax == 0) return VCG_OK;
-  const int rc = attn_check("vcg_bert_attn_fwd", qkv, ctx, stats, B, nh, Lmax, Lp);
+  int nT;
+  const int rc = attn_check("vcg_bert_attn_fwd", qkv, ctx, stats, B, nh, Lmax, Lp, &nT);
   if (rc != VCG_OK) return rc;
-  if (Lmax > LT) return bert_attn_long_fwd(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, scale, dropout_p, seed, s);
+  if (Lmax > LT)
+    return bert_attn_long_fwd(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, nT, scale, dropout_p, seed, s);
   hipLaunchKernelGGL(bert_attn_fwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, mask, (bf16_t*)ctx,
                      (float2*)stats, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
 }
 
-VCG_API int vcg_bert_attn_bwd(const void* qkv, const void* dctx, const void* ctx, const long long* mask,
-                              const void* stats, void* dqkv, int B, int nh, int L, int Lp, float scale,
-                              float dropout_p, unsigned long long seed, hipStream_t s) {
-  (void)ctx;  // (kept in the signature: the backward no longer needs the forward's output)
-  return vcg_bert_attn_bwd_varlen(qkv, dctx, mask, nullptr, stats, dqkv, B, nh, L, Lp, scale, dropout_p, seed, s);
+VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx, void* stats, int B, int nh, int L,
+                              int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
+  return vcg_bert_attn_fwd_varlen(qkv, mask, nullptr, ctx, stats, B, nh, L, Lp, scale, dropout_p, seed, s);
 }
 
 VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq,
@@ -434,13 +302,21 @@ VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const lo
     set_error("vcg_bert_attn_bwd: invalid arguments");
     return VCG_ERR_INVALID;
   }
-  const int rc = attn_check("vcg_bert_attn_bwd", qkv, dqkv, stats, B, nh, Lmax, Lp);
+  int nT;
+  const int rc = attn_check("vcg_bert_attn_bwd", qkv, dqkv, stats, B, nh, Lmax, Lp, &nT);
   if (rc != VCG_OK) return rc;
-  if (Lmax > LT)  // (the tiled backward keeps its D vector in the stats buffer's tail: vcg_bert_attn_stats_bytes)
-    return bert_attn_long_bwd(qkv, dctx, mask, seq, const_cast<void*>(stats), dqkv, B, nh, Lmax, Lp, scale, dropout_p,
-                              seed, s);
+  if (Lmax > LT)  // (the tiled backward keeps its D vector in the stats buffer's tail)
+    return bert_attn_long_bwd(qkv, dctx, mask, seq, const_cast<void*>(stats), dqkv, B, nh, Lmax, Lp, nT, scale,
+                              dropout_p, seed, s);
   hipLaunchKernelGGL(bert_attn_bwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, mask,
                      (const float2*)stats, (bf16_t*)dqkv, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
+}
+
+VCG_API int vcg_bert_attn_bwd(const void* qkv, const void* dctx, const void* ctx, const long long* mask,
+                              const void* stats, void* dqkv, int B, int nh, int L, int Lp, float scale,
+                              float dropout_p, unsigned long long seed, hipStream_t s) {
+  (void)ctx;  // (kept in the signature: the backward no longer needs the forward's output)
+  return vcg_bert_attn_bwd_varlen(qkv, dctx, mask, nullptr, stats, dqkv, B, nh, L, Lp, scale, dropout_p, seed, s);
 }

@@ -12,10 +12,10 @@
 // vcg_bn_apply_gram: per iteration a workgroup (4 waves) takes R = 16384 / C rows ([R][C] bf16 = 32 KiB of y):
 // every thread owns one 16-B channel chunk (8 channels: its scale / shift / column sums stay in registers) of
 // 8 rows, loads them one iteration ahead, applies fma(y, scale, shift) + ReLU, stores the bf16 a and its column
-// sums exactly as vcg_bn_apply_colsum, and writes the tile to LDS as [64-row k-step][128- or 64-column panel]
-// with the 16-B chunk swizzle of the weight-gradient engine (igemm_wgrad.hip wswz), from which ds_read_b64_tr_b16
-// gives each lane 4 consecutive rows of one column. The C x C Gram block pairs (jb <= kb of 16 x 16, the upper
-// triangle: G is symmetric) are dealt round-robin to the 4 waves and accumulated with v_mfma_f32_16x16x32_bf16
+// sums through the tail vcg_bn_apply_colsum uses (bn_steps.h colpart_tail), and writes the tile to LDS as
+// [64-row k-step][128- or 64-column panel] with the 16-B chunk swizzle of the weight-gradient engine
+// (igemm_wgrad.hip wswz), from which ds_read_b64_tr_b16 gives each lane 4 consecutive rows of one column.
+// The C x C Gram block pairs (jb <= kb of 16 x 16, the upper triangle: G is symmetric) are dealt round-robin to the 4 waves and accumulated with v_mfma_f32_16x16x32_bf16
 // over every row the workgroup sees (two LDS buffers, one barrier per iteration). Each workgroup writes a
 // [C * C + C] f32 slab (G mirrored to full, then colsum); gram_reduce sums the slabs in a fixed order in double
 // (deterministic).
@@ -30,7 +30,7 @@
 // then hold the centred Gc and d = colsum(a - c); gram_reduce sums them in double into g64 = [Gc | d | c] and
 // gram_finish writes the uncentred f32 G = Gc + d c^T + c d^T + M c c^T and colsum = d + M c; the statistics read
 // g64 (Cov = Gc / M - (d / M)(d / M)^T, mu = c + d / M: no cancellation against the centre).
-#include "common.h"
+#include "bn_steps.h"
 
 namespace vcg {
 namespace {
@@ -118,13 +118,13 @@ __device__ __forceinline__ void gram_body(const bf16_t* __restrict__ y, const fl
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int cc = tid % CPR, r0 = tid / CPR;  // this thread's chunk and first row of an iteration
-  float sc[8], sh[8], cs[8], ctr[8];
+  float sc[8], sh[8], cs[1][8], ctr[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sc[e] = scale[8 * cc + e];
     sh[e] = shift[8 * cc + e];
     ctr[e] = gram_centre(sc[e], sh[e], mean[8 * cc + e], invstd[8 * cc + e]);
-    cs[e] = 0.f;
+    cs[0][e] = 0.f;
   }
   if (blockIdx.x == 0 && W == 0 && tid < CPR) {  // (wave 0 holds every chunk once: CPR <= 32 threads)
 #pragma unroll
@@ -172,7 +172,7 @@ __device__ __forceinline__ void gram_body(const bf16_t* __restrict__ y, const fl
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           st[e] -= ctr[e];  // (exact in f32; exact in bf16 for a 0 centre and, by Sterbenz, for c / 2 <= a <= 2 c)
-          cs[e] += st[e];
+          cs[0][e] += st[e];
         }
         d.x = (uint32_t)f2bf(st[0]) | ((uint32_t)f2bf(st[1]) << 16);
         d.y = (uint32_t)f2bf(st[2]) | ((uint32_t)f2bf(st[3]) << 16);
@@ -217,15 +217,7 @@ __device__ __forceinline__ void gram_body(const bf16_t* __restrict__ y, const fl
       for (int r = 0; r < 4; ++r) sl[(k + r) * C + j] = acc[t][r];
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[tid * 9 + e] = cs[e];
-  __syncthreads();
-  for (int o = tid; o < C; o += 256) {
-    const int ch = o / 8, e = o % 8;
-    float s = 0.f;
-    for (int t = ch; t < 256; t += CPR) s += red[t * 9 + e];  // fixed order
-    sl[C * C + o] = s;
-  }
+  colpart_tail<1, 8, 9>(red, cs, CPR, nullptr, sl + C * C);
 }
 
 template <int C>

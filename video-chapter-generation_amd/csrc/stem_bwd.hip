@@ -1,15 +1,15 @@
 // The stem's backward after the max-pool as ONE pass: the max-pool backward, the stem BatchNorm + ReLU backward
-// (the apply of maxpool_bwd2_kernel MP_APPLY) and the 7x7 / stride-2 stem conv's weight gradient, without the
-// conv-output gradient dy0 ever reaching HBM (reference: the stem conv1 -> bn1 -> relu -> maxpool of
+// (the apply of maxpool_bwd_kernel MP_APPLY, 2x2-block form) and the 7x7 / stride-2 stem conv's weight gradient,
+// without the conv-output gradient dy0 ever reaching HBM (reference: the stem conv1 -> bn1 -> relu -> maxpool of
 // model/vision/resnet50_tsm.py's torchvision ResNet-50; only the weight gradient is needed -- the frames take none).
 //
 // Unfused, the stem backward writes dy0 [N][112][112][64] (1.64 GB at the C3 batch) in the apply pass and reads it
 // back in the im2col weight-gradient GEMM (plus the frames 28x through L2). Here a workgroup walks a contiguous range
 // of tiles; a tile is one row pair (2k, 2k + 1) of the conv output of one image = the 2x2 pixel blocks of pooled row
-// k (maxpool_bwd2_kernel's blocks), 2W pixels:
+// k (the blocks of maxpool_bwd_kernel's 2x2-block form), 2W pixels:
 //   phase 1: per (block, 8-channel chunk) thread: the <= 4 windows' pooled gradient + argmax bytes and the 4 pixels'
-//            conv output y, exactly the arithmetic of maxpool_bwd2_kernel<MP_APPLY> (window order, ReLU mask,
-//            rounding of g, bn_bwd_apply's affine map, rounding of dy0) -> dy0 tile [2W][64] bf16 in LDS;
+//            conv output y, exactly the arithmetic of maxpool_bwd_kernel<MP_APPLY> (window order, ReLU mask,
+//            rounding of g, the affine map of bn_steps.h, rounding of dy0) -> dy0 tile [2W][64] bf16 in LDS;
 //            the 9 input rows 4k - 3 .. 4k + 5 as pair-packed super pixels (2 pixels x RGB0 = 16 B) -> LDS;
 //   phase 2: dW[co][n] += sum_pix dy0[pix][co] P[pix][n], n = (kh, kwp, j, ci) the pair-packed stem layout
 //            (igemm.hip pair_taps: K = 7 x 4 x 8 = 224), both operands read with ds_read_b64_tr_b16 (4
@@ -20,6 +20,7 @@
 // 512-thread workgroup per CU with the next tile's loads in registers under the MFMA phase 1.43 ms; with a 2-slot
 // LDS-DMA ring a tile ahead 1.63 ms -- phase 1 is VALU-bound and ran with only 2 waves per SIMD, none overlapping.) Each workgroup writes its [64][224] fp32 slab; stem_wgrad_reduce_kernel sums
 // the slabs in a fixed order (deterministic) into the OIHW weight gradient.
+#include "bn_steps.h"
 #include "igemm.h"
 
 #ifndef VCG_STEM_BWD_DBG
@@ -121,18 +122,18 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
   const __amdgpu_buffer_rsrc_t ir = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.idx), 0, ibytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, xbytes, 0x00020000);
 
-  // bn_bwd_apply's per-channel map (maxpool_bwd2_kernel MP_APPLY, same arithmetic) in LDS: [sc, sh, A, Bc, Cc][64]
+  // the BN backward's per-channel map (bn_steps.h bn_bwd_coef, the step of maxpool_bwd_kernel MP_APPLY) in LDS:
+  // [sc, sh, A, Bc, Cc][64]
   __shared__ __attribute__((aligned(16))) float prm[5][64];
   if (tid < 64) {
     const int c = tid;
-    const float is = a.invstd[c];
-    const float A = (a.gamma ? a.gamma[c] : 1.f) * is;
-    const float Bc = -A * is * a.sum_gx[c] * a.inv_count;
+    float A, Bc, Cc;
+    bn_bwd_coef(a.gamma ? a.gamma[c] : 1.f, a.invstd[c], a.sum_gx[c], a.sum_g[c], a.mean[c], a.inv_count, A, Bc, Cc);
     prm[0][c] = a.msc[c];
     prm[1][c] = a.msh[c];
     prm[2][c] = A;
     prm[3][c] = Bc;
-    prm[4][c] = -A * a.sum_g[c] * a.inv_count - Bc * a.mean[c];
+    prm[4][c] = Cc;
   }
   const int ksteps = (2 * W + 31) / 32;  // k = the tile's 2W pixels, padded to 32 with zero dy0 rows
   for (int i = 2 * W * 8 + tid; i < ksteps * 32 * 8; i += SB_NTH)  // (the pad rows, never DMA'd)
@@ -244,8 +245,8 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           float v = fmaf(yv[e + h], sc[e + h], sh[e + h]) > 0.f ? acc[e + h] : 0.f;
-          const float gr = bf2f(f2bf(v));  // the gradient as maxpool_bwd2_kernel stores / recomputes it
-          d[h] = a.train ? fmaf(A[e + h], gr, fmaf(Bc[e + h], yv[e + h], Cc[e + h])) : A[e + h] * gr;
+          const float gr = bf2f(f2bf(v));  // the gradient as maxpool_bwd_kernel stores / recomputes it
+          d[h] = bn_bwd_map(a.train, A[e + h], Bc[e + h], Cc[e + h], gr, yv[e + h]);
         }
         o[e >> 1] = (uint32_t)f2bf(d[0]) | ((uint32_t)f2bf(d[1]) << 16);
       }

@@ -437,6 +437,21 @@ VCG_API int vcg_infonce_reduce_f32(const float* key_logits, long long ldz, const
 VCG_API int vcg_infonce_dz_f32(float* key_logits, long long ldz, const float* lse, float scale, int N, int K, hipStream_t stream);
 VCG_API int vcg_infonce_dq_pos(int dtype, float* dq, const void* k, const float* one_minus_p0, float scale, int N, int H, hipStream_t stream);
 
+/* ---- listwise (ListNet) fine-tuning (listnet.hip): model/lang/bert_hugface_listnet.py:148-176, trained by
+ *      train_lang/train_listwise.py. P [B S][H] is the pooled BERT output in `dtype` (16-B aligned); 2 <= S <=
+ *      vcg_listnet_max_slate() (64), H a multiple of 8 up to vcg_listnet_max_hidden() (8192), B >= 1, M >= 1. The
+ *      caller guarantees sel[m] in [0, B S) and cls[m] in {0, 1}. ------------------------------------------------- */
+VCG_API int vcg_listnet_max_slate(void);
+VCG_API int vcg_listnet_max_hidden(void);
+/* Slate b (rows r0 = b S ..): z_j = <P[r0], P[r0 + j]>, p = softmax(z) (maximum subtracted) -> p [B][S - 1],
+   l_b = -sum_j targets[b][j] log(p_j + 1e-10). Selected row m: logits [M][2] = W P[sel[m]] + bias (W fp32 [2][H]),
+   prob = softmax, ce_m = logsumexp - logits[m][cls[m]]. part [B + M] = the l_b, then the ce_m;
+   loss3 = {surrogate + binary, surrogate = mean_b l_b, binary = mean_m ce_m}. One launch plus a one-workgroup mean. */
+VCG_API int vcg_listnet_fwd(int dtype, const void* P, const float* targets, const long long* sel, const long long* cls, const float* W, const float* bias, int B, int S, int H, int M, float* p, float* logits, float* prob, float* part, float* loss3, hipStream_t stream);
+/* One launch: dP (fp32 [B S][H], every row written exactly once) for the upstream scalar dloss[0] (device);
+   dW [2][H] and db [2] (both or neither NULL) are ADDED to, in the order of m. No atomics; duplicate sel add. */
+VCG_API int vcg_listnet_bwd(int dtype, const void* P, const float* targets, const long long* sel, const long long* cls, const float* W, const float* p, const float* prob, const float* dloss, int B, int S, int H, int M, float* dP, float* dW, float* db, hipStream_t stream);
+
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148
  * (bucketed gradient all-reduce on every backward) and the parameter broadcast of :261-263. One communicator per

@@ -182,3 +182,82 @@ class InferYoutubeClipDataset(torch.utils.data.Dataset):
             nums = [int(p.rsplit("/", 1)[-1].split(".")[0]) for p in info["image_paths"]]
             img = normalize_frames(self.c.frames(info["vid"], [x - 1 for x in nums]))
         return img, ids, mask, info["clip_label"]
+
+
+class YoutubeListwiseClipDataset(torch.utils.data.Dataset):
+    """The listwise stage's slates (data.youtube_dataset.YoutubeListwiseClipDataset) over a SyntheticVideoCorpus: item
+    i = two positive clips and `negative_clip_num` negatives of video i. A corpus with a video that has fewer is refused
+    at construction (random.sample would raise in the middle of an epoch)."""
+
+    def __init__(self, corpus, tokenizer, clip_frame_num, max_text_len, negative_clip_num=10, mode="text"):
+        self.c, self.tok, self.T, self.L, self.mode = corpus, tokenizer, clip_frame_num, max_text_len, mode
+        self.negative_clip_num = negative_clip_num
+        for vid in corpus.vids:
+            lab = self._windows(vid)[1]
+            n_pos, n_neg = int(lab.sum()), int((lab == 0).sum())
+            if n_pos < 2 or n_neg < negative_clip_num:
+                raise ValueError(f"synthetic listwise dataset: video {vid} ({corpus.image_num[vid]} s) has {n_pos} "
+                                 f"positive and {n_neg} negative clips of {clip_frame_num} s, need 2 and "
+                                 f"{negative_clip_num}")
+
+    def _windows(self, vid):
+        n = self.c.image_num[vid]
+        win = cw.clip_windows(n, self.T)
+        cps = cw.cut_points_from_timestamps(self.c.timestamps[vid], n, mode="eval")
+        return win, cw.clip_labels(win, cps, self.T)
+
+    def __len__(self):
+        return len(self.c.vids)
+
+    def __getitem__(self, i):
+        from .youtube_dataset import listwise_item, listwise_slate
+        vid = self.c.vids[i]
+        n = self.c.image_num[vid]
+        win, lab = self._windows(vid)
+        slate = listwise_slate(lab, self.negative_clip_num)
+        frames_of = (lambda s: None) if self.mode == "text" else (
+            lambda s: self.c.frames(vid, cw.frame_numbers(s, self.T, n) - 1))
+        return listwise_item(slate, win, self.c.subtitles[vid], self.tok, self.L, frames_of)
+
+
+class InferYoutubeVideoDataset(torch.utils.data.Dataset):
+    """One chosen video's clips from start to end (data.infer_youtube_video_dataset.InferYoutubeVideoDataset) over a
+    SyntheticVideoCorpus: the listwise driver's test pass."""
+
+    max_offset = 2
+
+    def __init__(self, corpus, tokenizer, clip_frame_num, max_text_len, mode="text"):
+        self.c, self.tok, self.T, self.L, self.mode = corpus, tokenizer, clip_frame_num, max_text_len, mode
+        self.vids = list(corpus.vids)
+        self.infer_vid = None
+
+    def manual_choose_vid(self, vid):
+        if vid not in self.vids:
+            raise RuntimeError(f"The vid {vid} is not existed in dataset")
+        self.infer_vid = vid
+        self.cut_points = cw.cut_points_from_timestamps(self.c.timestamps[vid], self.c.image_num[vid], mode="eval")
+
+    def random_choose_vid(self):
+        self.manual_choose_vid(random.sample(self.vids, 1)[0])
+
+    def _chosen(self):
+        if self.infer_vid is None:
+            raise RuntimeError("You should run choose_vid before iterate this dataset")
+
+    def get_duration(self):
+        return self.c.image_num[self.infer_vid]
+
+    def __len__(self):
+        self._chosen()
+        return len(cw.clip_windows(self.get_duration(), self.T, self.max_offset))
+
+    def __getitem__(self, i):
+        from .infer_youtube_video_dataset import video_clip_item
+        self._chosen()
+        n = self.get_duration()
+        win = cw.clip_windows(n, self.T, self.max_offset)
+        ids, mask, label = video_clip_item(win, i, self.cut_points, self.c.subtitles[self.infer_vid], self.tok, self.T,
+                                           self.L)
+        img = 0 if self.mode == "text" else normalize_frames(
+            self.c.frames(self.infer_vid, cw.frame_numbers(int(win[i, 0]), self.T, n) - 1))
+        return img, ids, mask, label

@@ -1,5 +1,6 @@
-"""Drop-ins for reference data/youtube_dataset.py `YoutubeClipDataset` (:23-194) and `WindowClipDataset`
-(:359-536, the window model's sampler): training samplers over videos on disk. Same constructor, same sample tuple, same index / label / text / frame-file rules:
+"""Drop-ins for reference data/youtube_dataset.py `YoutubeClipDataset` (:23-194), `WindowClipDataset`
+(:359-536, the window model's sampler) and `YoutubeListwiseClipDataset` (:1195-1388, the listwise stage's slates, see
+the class): training samplers over videos on disk. Same constructor, same sample tuple, same index / label / text / frame-file rules:
 
     YoutubeClipDataset(img_dir, data_file, vid_file, tokenizer, clip_frame_num, max_text_len, mode="all",
                        transform=None, target_transform=None, subtitle_dir=None)
@@ -182,3 +183,82 @@ class WindowClipDataset(torch.utils.data.Dataset):
         info = cw.window_clip_info(win, target, T, self.window_size, image_num, max_offset)
         clip_info = {k: torch.as_tensor(v) for k, v in info.items()}
         return img_clips, torch.stack(ids), torch.stack(masks), torch.tensor(1 if is_positive else 0), clip_info
+
+
+def listwise_slate(labels, negative_clip_num, rng=random):
+    """Clip indices of one slate (reference youtube_dataset.py:1283-1293): two positives, then `negative_clip_num`
+    negatives, by two `random.sample` draws in that order. A video with fewer is random.sample's ValueError, as in the
+    reference."""
+    pos = np.nonzero(labels == 1)[0].tolist()
+    neg = np.nonzero(labels == 0)[0].tolist()
+    return rng.sample(pos, k=2) + rng.sample(neg, k=negative_clip_num)
+
+
+def listwise_item(slate, win, subtitles, tokenizer, max_text_len, frames_of):
+    """(img_clips, text_ids [S, L], attention_masks [S, L], labels [S] = 1, 1, 0, ...) of the slate's clips (:1295-1385).
+    frames_of(start): the clip's raw frames u8 [T, H, W, 3], or None in text mode (the dummy image 0 per clip)."""
+    imgs, ids, masks = [], [], []
+    for k in slate:
+        s, e = win[k].tolist()
+        i, m = cw.encode_text(tokenizer, cw.window_text(subtitles, s, e), max_text_len)
+        ids.append(torch.from_numpy(i))
+        masks.append(torch.from_numpy(m))
+        fr = frames_of(s)
+        imgs.append(torch.from_numpy(np.array(0) if fr is None else np.asarray(fr)).float())
+    labels = torch.from_numpy(np.array([1, 1] + [0] * (len(slate) - 2))).long()
+    return torch.stack(imgs, dim=0), torch.stack(ids, dim=0), torch.stack(masks, dim=0), labels
+
+
+class YoutubeListwiseClipDataset(torch.utils.data.Dataset):
+    """Reference youtube_dataset.py:1195-1388: item i is a slate of video i's clips, two positive clips first and then
+    `negative_clip_num` negatives:
+
+        (img_clips, text_ids i64 [S, L], attention_masks i64 [S, L], labels i64 [S] = 1, 1, 0, ...), S = 2 + negatives
+
+    Cut points are kept for 4 <= sec <= N - 4 (:1251-1254); windows, IoU labels, subtitles and the frame-file rule are
+    data/clip_windows.py's. In mode "text" img_clips is the dummy f32 [S] of zeros; in the other modes the reference
+    returns the RAW decoded frames as floats, f32 [S, T, H, W, 3] -- `transform` is accepted and never applied
+    (:1351-1354, :1374) -- and so does this."""
+
+    def __init__(self, img_dir, data_file, vid_file, tokenizer, clip_frame_num, max_text_len, negative_clip_num=10,
+                 mode="all", transform=None, target_transform=None, subtitle_dir=None):
+        self.tokenizer = tokenizer
+        self.clip_frame_num = clip_frame_num
+        self.max_text_len = max_text_len
+        self.negative_clip_num = negative_clip_num
+        self.mode = mode
+        self.half_clip_frame_num = int(clip_frame_num // 2)
+        self.img_dir = img_dir
+        vids, titles, durations, timestamps = parse_csv_to_list(data_file)
+        self.vid2title = dict(zip(vids, titles))
+        self.vid2timestamps = dict(zip(vids, timestamps))
+        self.vid2durations = dict(zip(vids, durations))
+        with open(vid_file) as f:
+            self.vids = [x.strip() for x in f.readlines()]
+        self.vid2asr_files = subtitle_files(os.path.dirname(data_file) if subtitle_dir is None else subtitle_dir)
+        self.transform = transform
+        self.target_transform = target_transform
+
+    def __len__(self):
+        return len(self.vids)
+
+    def __getitem__(self, i):
+        vid = self.vids[i]
+        image_path = os.path.join(self.img_dir, vid)
+        image_num = len(glob.glob(image_path + "/*.jpg"))
+        with open(self.vid2asr_files[vid]) as f:
+            subtitles = json.load(f)
+        T = self.clip_frame_num
+        cut_points = cw.cut_points_from_timestamps(self.vid2timestamps[vid], image_num, mode="eval")
+        win = cw.clip_windows(image_num, T)
+        if len(win) == 0:
+            raise ValueError(f"video {vid}: {image_num} frames is shorter than one clip")
+        slate = listwise_slate(cw.clip_labels(win, cut_points, T), self.negative_clip_num)
+
+        def frames_of(s):
+            if self.mode == "text":
+                return None
+            nums = cw.frame_numbers(s, T, image_num)
+            return frames_tensor([os.path.join(image_path, "%05d.jpg" % n) for n in nums.tolist()], None, True).numpy()
+
+        return listwise_item(slate, win, subtitles, self.tokenizer, self.max_text_len, frames_of)

@@ -201,7 +201,8 @@ def build_model(args, device):
     return _build(args.data_mode, clip_frame_num=args.clip_frame_num, hidden_size=128, head_type=args.head_type,
                   model_type=args.model_type, seed=args.seed, device=device, precision=args.precision,
                   lang_pretrain_ckpt=getattr(args, "lang_pretrain_ckpt", None),
-                  lang_contrast_ckpt=getattr(args, "lang_contrast_ckpt", None))
+                  lang_contrast_ckpt=getattr(args, "lang_contrast_ckpt", None),
+                  lang_listnet_ckpt=getattr(args, "lang_listnet_ckpt", None))
 
 
 def make_tokenizer(vocab_file):
@@ -257,6 +258,8 @@ def main(argv=None):
                    help="pretrain_lang_model_hugface.py checkpoint the language model starts from (:308,326-330)")
     p.add_argument("--lang_contrast_ckpt", default=None,
                    help="train_lang/pretrain_constrast_lang_model.py checkpoint the language model starts from instead")
+    p.add_argument("--lang_listnet_ckpt", default=None,
+                   help="train_lang/train_listwise.py checkpoint the language model starts from instead")
     # the reference's on-disk corpus (its hard-coded paths, :307-318): frames <img_dir>/<vid>/%05d.jpg, the dataset
     # CSV, the split's vid list, subtitles <subtitle_dir>/*/subtitle_<vid>.json, the validation clip JSON
     p.add_argument("--img_dir", default=None)

@@ -83,17 +83,57 @@ def load_contrast_pretrain(bert, path):
     bert.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}, strict=True)
 
 
-def _load_lang(bert, lang_pretrain_ckpt, lang_contrast_ckpt):
-    if lang_pretrain_ckpt and lang_contrast_ckpt:
-        raise ValueError("lang_pretrain_ckpt and lang_contrast_ckpt: one language-model checkpoint at most")
+def build_listnet_model(seed=None, device=None, precision="bf16", dropout=None, config=None):
+    """The listwise driver's model (train_lang/train_listwise.py:274-279): bert_hugface_listnet.BertHugface(
+    pretrain_stage=False) with build_chapter_head(). With a seed every parameter (surrogate_head included) is seeded by
+    name."""
+    from model.lang.bert_hugface_listnet import BertHugface
+    from vcg_hip.nn import BertConfig
+    cfg = config if config is not None else BertConfig(output_attentions=True)
+    if dropout is not None:
+        cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = dropout
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = BertHugface(pretrain_stage=False, config=cfg)
+    model.build_chapter_head()
+    if device is not None:
+        model = model.to(device)
+    if seed is not None:
+        synth.init_params(model, seed)
+    model.precision = precision
+    return model
+
+
+def load_listnet_pretrain(bert, path):
+    """The listwise stage's hand-off: `path` is train_lang/train_listwise.py's checkpoint, a bare
+    bert_hugface_listnet.BertHugface state dict (base_model.*, head.* [2, H], surrogate_head.*). `bert` is the scorer's
+    BertModel; its weights become the checkpoint's base_model.*, strictly. Anything else (the masked-LM or the
+    contrastive stage's checkpoint, say) is a ValueError."""
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    H = bert.config.hidden_size
+    hw = sd.get("head.weight") if isinstance(sd, dict) else None
+    if hw is None or "surrogate_head.weight" not in sd or not hasattr(hw, "shape") or tuple(hw.shape) != (2, H):
+        raise ValueError(f"{path}: not a listwise fine-tuning checkpoint (no surrogate_head.weight / [2, {H}] "
+                         f"head.weight)")
+    pre = "base_model."
+    bert.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}, strict=True)
+
+
+def _load_lang(bert, lang_pretrain_ckpt, lang_contrast_ckpt, lang_listnet_ckpt=None):
+    if sum(bool(c) for c in (lang_pretrain_ckpt, lang_contrast_ckpt, lang_listnet_ckpt)) > 1:
+        raise ValueError("lang_pretrain_ckpt, lang_contrast_ckpt and lang_listnet_ckpt: one language-model checkpoint "
+                         "at most")
     if lang_pretrain_ckpt:
         load_lang_pretrain(bert, lang_pretrain_ckpt)
     if lang_contrast_ckpt:
         load_contrast_pretrain(bert, lang_contrast_ckpt)
+    if lang_listnet_ckpt:
+        load_listnet_pretrain(bert, lang_listnet_ckpt)
 
 
 def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropout=None, seed=None, device=None,
-                     precision="fp32", bn_stats=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None):
+                     precision="fp32", bn_stats=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None,
+                     lang_listnet_ckpt=None):
     from model.fusion.two_stream import TwoStream
     from model.lang.bert_hugface import BertHugface
     from model.vision.resnet50_tsm import Resnet50TSM
@@ -116,7 +156,7 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
     if seed is not None:
         synth.init_params(model, seed)  # on the GPU this runs the HIP generator (bit-identical to numpy)
     # (after the seeded init, which covers every parameter)
-    _load_lang(model.lang_model, lang_pretrain_ckpt, lang_contrast_ckpt)
+    _load_lang(model.lang_model, lang_pretrain_ckpt, lang_contrast_ckpt, lang_listnet_ckpt)
     if bn_stats is not None:
         synth.load_bn_stats(model, bn_stats)
     model.precision = precision
@@ -124,14 +164,16 @@ def build_two_stream(clip_frame_num=16, hidden_size=128, head_type="mlp", dropou
 
 
 def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="mlp", model_type="r50tsm", seed=None,
-                device=None, precision="bf16", dropout=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None):
+                device=None, precision="bf16", dropout=None, lang_pretrain_ckpt=None, lang_contrast_ckpt=None,
+                lang_listnet_ckpt=None):
     """The driver's model by `--data_mode` (`train_video_segment_point.py:330-363`): "text" ->
     BertHugface + head, "image" -> Resnet50TSM (or Resnet50) + head, "all" -> TwoStream. lang_pretrain_ckpt: the
     masked-LM stage's checkpoint for the language model (`:326-330`; "all" and "text"); lang_contrast_ckpt: the
-    contrastive stage's instead."""
+    contrastive stage's instead; lang_listnet_ckpt: the listwise stage's instead."""
     if data_mode == "all":
         return build_two_stream(clip_frame_num, hidden_size, head_type, dropout, seed, device, precision,
-                                lang_pretrain_ckpt=lang_pretrain_ckpt, lang_contrast_ckpt=lang_contrast_ckpt)
+                                lang_pretrain_ckpt=lang_pretrain_ckpt, lang_contrast_ckpt=lang_contrast_ckpt,
+                                lang_listnet_ckpt=lang_listnet_ckpt)
     if data_mode == "text":
         from model.lang.bert_hugface import BertHugface
         from vcg_hip.nn import BertConfig
@@ -156,10 +198,11 @@ def build_model(data_mode="all", clip_frame_num=16, hidden_size=128, head_type="
         model = model.to(device)
     if seed is not None:
         synth.init_params(model, seed)
-    if lang_pretrain_ckpt or lang_contrast_ckpt:
+    if lang_pretrain_ckpt or lang_contrast_ckpt or lang_listnet_ckpt:
         if data_mode != "text":
-            raise ValueError("lang_pretrain_ckpt / lang_contrast_ckpt: the image-only model has no language model")
-        _load_lang(model.base_model, lang_pretrain_ckpt, lang_contrast_ckpt)
+            raise ValueError("lang_pretrain_ckpt / lang_contrast_ckpt / lang_listnet_ckpt: the image-only model has no "
+                             "language model")
+        _load_lang(model.base_model, lang_pretrain_ckpt, lang_contrast_ckpt, lang_listnet_ckpt)
     model.precision = precision
     return model
 

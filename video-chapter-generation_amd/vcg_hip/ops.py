@@ -1099,6 +1099,124 @@ def infonce(q, k, queue_km, K, inv_T, want_dq=False, want_logits=False):
     return lse, row_loss, loss, n_correct, dq, logits
 
 
+# ----------------------------------------------------------------------------- listwise fine-tuning (listnet.hip)
+def listnet_limits():
+    """(largest slate length S, largest hidden size H) of the listnet kernels; H must also be a multiple of 8."""
+    return _lib.query("vcg_listnet_max_slate"), _lib.query("vcg_listnet_max_hidden")
+
+
+def listnet_check_shape(B, S, H, M):
+    """The kernels' shape rules as ValueErrors, before anything is launched."""
+    max_s, max_h = listnet_limits()
+    if B < 1:
+        raise ValueError(f"listnet: batch size {B}, need at least 1 slate")
+    if S < 2 or S > max_s:
+        raise ValueError(f"listnet: slate length {S} outside [2, {max_s}] (the boundary clip and at least one other; "
+                         f"one lane of a wave per contrast clip)")
+    if H < 8 or H > max_h or H % 8 != 0:
+        raise ValueError(f"listnet: hidden size {H} must be a multiple of 8 in [8, {max_h}] (16-byte rows)")
+    if M < 1:
+        raise ValueError(f"listnet: {M} selected rows, need at least 1")
+
+
+class ListnetIndices:
+    """The boundary head's rows `sel` [M] (rows of P, duplicates allowed) and labels `cls` [M] in {0, 1}, checked on the
+    host against rows = B S -- an index out of range never reaches a kernel -- and their int64 device copies. Host
+    lists / arrays / CPU tensors are checked as they are; device tensors cost one small device-to-host copy."""
+
+    def __init__(self, sel, cls, rows, device):
+        sel, cls = (t if isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in (sel, cls))
+        if sel.dim() != 1 or cls.shape != sel.shape:
+            raise ValueError(f"listnet: sel {tuple(sel.shape)} and cls {tuple(cls.shape)} must be two vectors of one "
+                             f"length")
+        if sel.dtype.is_floating_point or cls.dtype.is_floating_point:
+            raise ValueError("listnet: sel and cls must be integer tensors")
+        if sel.is_cuda or cls.is_cuda:
+            host = torch.stack([sel.to(device, torch.int64), cls.to(device, torch.int64)]).cpu()
+            sel_h, cls_h = host[0], host[1]
+        else:
+            sel_h, cls_h = sel.to(torch.int64), cls.to(torch.int64)
+        self.M = sel_h.numel()
+        if self.M:
+            lo, hi = int(sel_h.min()), int(sel_h.max())
+            if lo < 0 or hi >= rows:
+                raise ValueError(f"listnet: selected row {lo if lo < 0 else hi} outside [0, {rows})")
+            bad = cls_h[(cls_h != 0) & (cls_h != 1)]
+            if bad.numel():
+                raise ValueError(f"listnet: binary label {int(bad[0])} outside {{0, 1}}")
+        self.rows = rows
+        self.sel = sel_h.contiguous().to(device)
+        self.cls = cls_h.contiguous().to(device)
+
+
+def _listnet_args(P_, targets, idx):
+    _chk(P_, None, "P")
+    _chk(targets, torch.float32, "targets")
+    if P_.dim() != 2 or targets.dim() != 2:
+        raise ValueError(f"listnet: P {tuple(P_.shape)} must be [B S, H] and targets {tuple(targets.shape)} [B, S]")
+    B, S = targets.shape
+    H = P_.shape[1]
+    listnet_check_shape(B, S, H, idx.M)
+    if P_.shape[0] != B * S or idx.rows != B * S:
+        raise ValueError(f"listnet: P has {P_.shape[0]} rows and the indices were checked against {idx.rows}; targets "
+                         f"[{B}, {S}] need {B * S}")
+    return B, S, H, idx.M
+
+
+def listnet_fwd(P_, targets, sel, cls, W, bias):
+    """The ListNet slate loss and the boundary head over the pooled output P [B S, H] (fp32 or bf16), targets fp32
+    [B, S], W fp32 [2, H], bias fp32 [2] -> (loss3 fp32 [3] = loss, surrogate, binary; binary_logits fp32 [M, 2];
+    binary_prob fp32 [M, 2]; p fp32 [B, S - 1]; the checked ListnetIndices for listnet_bwd). Every refusal is a
+    ValueError raised before the launch."""
+    if not isinstance(sel, ListnetIndices) and P_.dim() == 2 and targets.dim() == 2:
+        listnet_check_shape(targets.shape[0], targets.shape[1], P_.shape[1], len(sel))  # (the shape before the rows)
+    idx = sel if isinstance(sel, ListnetIndices) else ListnetIndices(sel, cls, P_.shape[0], P_.device)
+    B, S, H, M = _listnet_args(P_, targets, idx)
+    _chk(W, torch.float32, "W")
+    _chk(bias, torch.float32, "bias")
+    if tuple(W.shape) != (2, H) or bias.numel() != 2:
+        raise ValueError(f"listnet: the boundary head must be W [2, {H}] and bias [2], got {tuple(W.shape)} and "
+                         f"{tuple(bias.shape)}")
+    dev = P_.device
+    p = torch.empty((B, S - 1), dtype=torch.float32, device=dev)
+    logits = torch.empty((M, 2), dtype=torch.float32, device=dev)
+    prob = torch.empty((M, 2), dtype=torch.float32, device=dev)
+    part = torch.empty(B + M, dtype=torch.float32, device=dev)
+    loss3 = torch.empty(3, dtype=torch.float32, device=dev)
+    _lib.call("vcg_listnet_fwd", dt_code(P_.dtype), P(P_), P(targets), P(idx.sel), P(idx.cls), P(W), P(bias), B, S, H, M,
+              P(p), P(logits), P(prob), P(part), P(loss3), stream())
+    return loss3, logits, prob, p, idx
+
+
+def listnet_bwd(P_, targets, idx, W, p, prob, dloss, dW=None, db=None, out=None):
+    """dP fp32 [B S, H] (into `out` if given: every row is written exactly once) for the device scalar dloss; dW [2, H]
+    and db [2] (both or neither) are added to. idx: the ListnetIndices listnet_fwd returned."""
+    if not isinstance(idx, ListnetIndices):
+        raise TypeError("listnet_bwd: idx must be the ListnetIndices that listnet_fwd checked")
+    B, S, H, M = _listnet_args(P_, targets, idx)
+    _chk(W, torch.float32, "W")
+    _chk(p, torch.float32, "p")
+    _chk(prob, torch.float32, "prob")
+    _chk(dloss, torch.float32, "dloss")
+    if tuple(W.shape) != (2, H) or tuple(p.shape) != (B, S - 1) or tuple(prob.shape) != (M, 2) or dloss.numel() != 1:
+        raise ValueError("listnet_bwd: shapes of W / p / prob / dloss do not agree with P and targets")
+    if (dW is None) != (db is None):
+        raise ValueError("listnet_bwd: dW and db go together")
+    if dW is not None:
+        _chk(dW, torch.float32, "dW")
+        _chk(db, torch.float32, "db")
+        if tuple(dW.shape) != (2, H) or db.numel() != 2:
+            raise ValueError("listnet_bwd: dW must be [2, H] and db [2]")
+    if out is None:
+        out = torch.empty((B * S, H), dtype=torch.float32, device=P_.device)
+    _chk(out, torch.float32, "out")
+    if tuple(out.shape) != (B * S, H):
+        raise ValueError(f"listnet_bwd: out {tuple(out.shape)} must be [{B * S}, {H}]")
+    _lib.call("vcg_listnet_bwd", dt_code(P_.dtype), P(P_), P(targets), P(idx.sel), P(idx.cls), P(W), P(p), P(prob),
+              P(dloss), B, S, H, M, P(out), P(dW), P(db), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- optimiser
 def sumsq(x, out, workspace=None):
     if workspace is None:

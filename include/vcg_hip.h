@@ -30,6 +30,10 @@ enum { VCG_F32 = 0, VCG_BF16 = 1 };
 enum { VCG_GRAD_F32 = 0x10 };
 enum { VCG_OK = 0, VCG_ERR_INVALID = -1, VCG_ERR_UNSUPPORTED = -2, VCG_ERR_HIP = -3 };
 enum { VCG_ACT_NONE = 0, VCG_ACT_RELU = 1, VCG_ACT_GELU = 2, VCG_ACT_TANH = 3, VCG_ACT_GELU_BWD = 4 };
+/* the tanh form 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) (transformers' NewGELUActivation, what OpenAIGPT's
+   afn = "gelu" resolves to) and its derivative of a residual, wherever VCG_ACT_GELU / VCG_ACT_GELU_BWD are taken by
+   vcg_gemm's dense GEMMs (the wide-tile engine, the 128 x 128 engines, fp32: tanhf) */
+enum { VCG_ACT_GELU_TANH = 5, VCG_ACT_GELU_TANH_BWD = 6 };
 /* vcg_gemm act flag: with a residual, round alpha * AB + bias to the storage dtype BEFORE adding the residual (the
    unfolded conv3 -> bn3 path stores y3 in bf16; the scoring forward's folded conv3 sets it to match). Without it the
    residual is added to the f32 accumulator value. */
@@ -296,6 +300,26 @@ VCG_API int vcg_bert_attn_bwd(const void* qkv, const void* dctx, const void* ctx
    keep the padded [B*nh][Lmax] space */
 VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq, const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
+/* the same with flags: VCG_ATTN_CAUSAL -- key j is visible to query i iff j <= i and its mask entry is set (a decoder:
+   transformers OpenAIGPTModel, reference model/lang/gpt_hugface.py). A query without any visible key (its sequence's
+   leading keys masked) keeps the convention above: uniform over all L keys in range, which is HF's result for a fully
+   masked sequence; for a LEFT-padded mask HF attends to the future valid keys instead (its -1e4 causal fill is finite)
+   and this library does not. Tiles wholly above the diagonal are skipped. flags 0: the _varlen functions; seq NULL:
+   padded. vcg_attn_softmax_fwd_ex / _bwd_ex: the unfused chain's softmax under the same rule.
+   Gradient: none reaches the score of a future key, as under HF's `w * b + -1e4 (1 - b)` fill -- P is zero there
+   except in a row without a visible key, where dS is cut while D = rowsum(dP o P) still runs over every key. */
+enum { VCG_ATTN_CAUSAL = 1 };
+VCG_API int vcg_bert_attn_fwd_ex(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, int flags, hipStream_t s);
+VCG_API int vcg_bert_attn_bwd_ex(const void* qkv, const void* dctx, const long long* mask, const int* seq, const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale, float dropout_p, unsigned long long seed, int flags, hipStream_t s);
+VCG_API int vcg_attn_softmax_fwd_ex(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh, int L, int Lp, float scale, float dropout_p, unsigned long long seed, int flags, hipStream_t s);
+VCG_API int vcg_attn_softmax_bwd_ex(int dtype, const void* dPd, const void* P, void* dS, int Z, int L, int Lp, float scale, float dropout_p, unsigned long long seed, int flags, hipStream_t s);
+/* OpenAIGPT's embedding (transformers OpenAIGPTModel.forward): out[b, t] = dropout(tok[ids[b, t]] + pos[t]), no token
+   types and no LayerNorm; the dropout counter of element (row, h) is row * H + h. Backward: fp32 token and position
+   gradients of dout (bf16, or fp32 with VCG_GRAD_F32) through the same dropout, accumulated in a fixed order without
+   atomics (vcg_embed_ln_bwd's scatter; added onto tok_grad / pos_grad, either may be NULL); ws:
+   vcg_ln_bwd_ws_bytes(B * L, H) bytes, the shape limits of vcg_embed_ln_bwd. */
+VCG_API int vcg_gpt_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B, int L, int H, float dropout_p, unsigned long long seed, hipStream_t s);
+VCG_API int vcg_gpt_embed_bwd(int dtype, const void* dout, const long long* ids, float* tok_grad, float* pos_grad, float* ws, long long ws_bytes, int B, int L, int H, float dropout_p, unsigned long long seed, hipStream_t s);
 VCG_API int vcg_tanh_bwd(int dtype, const void* dy, const void* t, void* dx, long long n, hipStream_t s);
 
 /* ---- fusion head + loss (head.hip): ChapterHead mlp (two_stream.py:51-95), softmax (:189),

@@ -205,6 +205,32 @@ __global__ void embed_type_kernel(const float* __restrict__ tmp, float* __restri
   type_grad[c] += (float)tot;
 }
 
+// ---------------------------------------------------------------- GPT embedding (no token types, no LayerNorm)
+// out[row] = dropout(tok[ids[row]] + pos[row % L]); one workgroup per row, counter row * H + c
+template <typename T>
+__global__ void gpt_embed_fwd_kernel(const long long* __restrict__ ids, const float* __restrict__ tok,
+                                     const float* __restrict__ pos, T* __restrict__ out, int L, int H, float p,
+                                     uint64_t seed) {
+  const int row = blockIdx.x;
+  const int l = row % L;
+  const long long id = ids[row];
+  for (int c = threadIdx.x; c < H; c += blockDim.x) {
+    const long long idx = (long long)row * H + c;
+    const float v = tok[id * H + c] + pos[(long long)l * H + c];
+    out[idx] = from_f<T>(keep(seed, idx, p) ? v / (1.f - p) : 0.f);
+  }
+}
+
+// de[row] = dropout'(dout[row]) in fp32: the rows embed_scatter_kernel / embed_pos_kernel then sum in a fixed order
+template <typename T>
+__global__ void gpt_embed_bwd_kernel(const T* __restrict__ dout, float* __restrict__ de, long long n, float p,
+                                     uint64_t seed) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const float d = to_f<T>(dout[idx]);
+  de[idx] = keep(seed, idx, p) ? d / (1.f - p) : 0.f;
+}
+
 // ---------------------------------------------------------------- residual LayerNorm
 // out = LN(dropout(x) + res)
 template <typename T>
@@ -361,8 +387,9 @@ template <typename T> __device__ __forceinline__ void st2(T* p, float a, float b
 }
 
 // One wave per score row; lane l owns key pairs j = 2l + 128e (e < 4: L <= 512, Lp even): 4-B (bf16)
-// / 8-B (fp32) loads and stores.
-template <typename T>
+// / 8-B (fp32) loads and stores. CAUSAL: key j counts as masked for query row < j (the fused kernels' rule,
+// bert_attn_steps.h); a row without a visible key stays uniform over all L keys.
+template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_softmax_fwd_kernel(const T* __restrict__ S,
                                                                const long long* __restrict__ mask,
                                                                T* __restrict__ P, T* __restrict__ Pd, int nh, int L,
@@ -383,8 +410,8 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_kernel(const T* __restri
     if (j < L) {
       float a, c;
       ld2<T>(S + base + j, a, c);
-      const bool k0 = mask == nullptr || mask[(long long)b * L + j] != 0;
-      const bool k1 = j + 1 < L && (mask == nullptr || mask[(long long)b * L + j + 1] != 0);
+      const bool k0 = (mask == nullptr || mask[(long long)b * L + j] != 0) && (!CAUSAL || j <= row);
+      const bool k1 = j + 1 < L && (mask == nullptr || mask[(long long)b * L + j + 1] != 0) && (!CAUSAL || j + 1 <= row);
       v[e][0] = k0 ? a * scale : -INFINITY;
       v[e][1] = k1 ? c * scale : -INFINITY;
       mx = fmaxf(mx, fmaxf(v[e][0], v[e][1]));
@@ -421,8 +448,10 @@ __global__ __launch_bounds__(256) void attn_softmax_fwd_kernel(const T* __restri
   }
 }
 
-// dS = scale * P o (dP - rowsum(dP o P)), dP = dPd o mask/(1-p); same lane layout as the forward
-template <typename T>
+// dS = scale * P o (dP - rowsum(dP o P)), dP = dPd o mask/(1-p); same lane layout as the forward. CAUSAL: no
+// gradient reaches the score of a future key (j > row) -- P is zero there except in a row without a visible key
+// (uniform over all L keys), where HF's `w * b` fill cuts the gradient while D still sums over every key.
+template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_softmax_bwd_kernel(const T* __restrict__ dPd, const T* __restrict__ P,
                                                                T* __restrict__ dS, int L, int Lp, float scale, float p,
                                                                uint64_t seed, int Z) {
@@ -452,8 +481,8 @@ __global__ __launch_bounds__(256) void attn_softmax_bwd_kernel(const T* __restri
   for (int e = 0; e < MAXE; ++e) {
     const int j = 2 * lane + 128 * e;
     if (j < Lp)
-      st2<T>(dS + base + j, j < L ? scale * pr[e][0] * (dp[e][0] - dot) : 0.f,
-             j + 1 < L ? scale * pr[e][1] * (dp[e][1] - dot) : 0.f);
+      st2<T>(dS + base + j, j < L && (!CAUSAL || j <= row) ? scale * pr[e][0] * (dp[e][0] - dot) : 0.f,
+             j + 1 < L && (!CAUSAL || j + 1 <= row) ? scale * pr[e][1] * (dp[e][1] - dot) : 0.f);
   }
 }
 
@@ -837,6 +866,58 @@ VCG_API int vcg_embed_ln_bwd(int dtype, const void* dout, const long long* ids, 
   return VCG_OK;
 }
 
+VCG_API int vcg_gpt_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B,
+                              int L, int H, float dropout_p, unsigned long long seed, hipStream_t s) {
+  VCG_REQUIRE(ids && tok && pos && out && B >= 0 && L >= 0 && H > 0, "invalid arguments");
+  VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
+  if (B * L == 0) return VCG_OK;
+  if (dtype == VCG_BF16)
+    hipLaunchKernelGGL(gpt_embed_fwd_kernel<bf16_t>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (bf16_t*)out, L, H,
+                       dropout_p, (uint64_t)seed);
+  else
+    hipLaunchKernelGGL(gpt_embed_fwd_kernel<float>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (float*)out, L, H,
+                       dropout_p, (uint64_t)seed);
+  VCG_LAUNCH_CHECK();
+  return VCG_OK;
+}
+
+// GPT embedding backward: dropout backward into fp32 rows, then vcg_embed_ln_bwd's scatter into the token / position
+// grads (fp32, accumulated onto what is there, fixed order, no atomics).
+VCG_API int vcg_gpt_embed_bwd(int dtype, const void* dout, const long long* ids, float* tok_grad, float* pos_grad,
+                              float* ws, long long ws_bytes, int B, int L, int H, float dropout_p,
+                              unsigned long long seed, hipStream_t s) {
+  const int rows = B * L;
+  VCG_REQUIRE(dout && ids && ws && B >= 0 && L >= 0 && H > 0, "invalid arguments");
+  VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
+  if (rows == 0) return VCG_OK;
+  VCG_REQUIRE(ws_bytes >= vcg_ln_bwd_ws_bytes(rows, H), "workspace too small");
+  VCG_REQUIRE(H <= SCAT_MAXE * 256, "hidden size > 1024 not supported by the token-grad reduction");
+  if (dtype & VCG_GRAD_F32) dtype = VCG_F32;
+  int rpb;
+  const int nb = row_blocks(rows, &rpb);
+  VCG_REQUIRE(L <= 2 * nb, "L > 2 * row blocks: the per-position sums would not fit the partial region");
+  float* part = ws;  // (embed_pos_kernel's [L][H] per-position sums; not read here)
+  float* de = ws + (long long)nb * 2 * H;
+  const long long n = (long long)rows * H;
+  if (dtype == VCG_BF16)
+    hipLaunchKernelGGL(gpt_embed_bwd_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       (const bf16_t*)dout, de, n, dropout_p, (uint64_t)seed);
+  else
+    hipLaunchKernelGGL(gpt_embed_bwd_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       (const float*)dout, de, n, dropout_p, (uint64_t)seed);
+  VCG_LAUNCH_CHECK();
+  if (tok_grad) {
+    hipLaunchKernelGGL(embed_scatter_kernel, dim3(rows), dim3(256), 0, s, de, ids, tok_grad, H, (long long)rows,
+                       (long long)-1);
+    VCG_LAUNCH_CHECK();
+  }
+  if (pos_grad) {
+    hipLaunchKernelGGL(embed_pos_kernel, dim3((H + 255) / 256, L), dim3(256), 0, s, de, pos_grad, part, B, L, H);
+    VCG_LAUNCH_CHECK();
+  }
+  return VCG_OK;
+}
+
 VCG_API int vcg_ln_fwd(int dtype, const void* x, const void* res, const float* gamma, const float* beta, void* out,
                        float* mean, float* rstd, int rows, int H, float eps, float dropout_p, unsigned long long seed,
                        hipStream_t s) {
@@ -995,32 +1076,62 @@ VCG_API int vcg_colsum(int dtype, const void* x, long long ld, int rows, int N, 
   return VCG_OK;
 }
 
-VCG_API int vcg_attn_softmax_fwd(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh,
-                                 int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
+template <bool CAUSAL>
+static int attn_softmax_fwd(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh, int L,
+                            int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
   VCG_REQUIRE(L <= 512 && Lp >= L && Lp % 2 == 0 && Lp <= 512, "L must be <= 512, Lp even");
   dim3 grid((L + 3) / 4, B * nh);
   if (dtype == VCG_BF16)
-    hipLaunchKernelGGL(attn_softmax_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)S, mask, (bf16_t*)P,
-                       (bf16_t*)Pd, nh, L, Lp, scale, dropout_p, (uint64_t)seed);
+    hipLaunchKernelGGL((attn_softmax_fwd_kernel<bf16_t, CAUSAL>), grid, dim3(256), 0, s, (const bf16_t*)S, mask,
+                       (bf16_t*)P, (bf16_t*)Pd, nh, L, Lp, scale, dropout_p, (uint64_t)seed);
   else
-    hipLaunchKernelGGL(attn_softmax_fwd_kernel<float>, grid, dim3(256), 0, s, (const float*)S, mask, (float*)P,
-                       (float*)Pd, nh, L, Lp, scale, dropout_p, (uint64_t)seed);
+    hipLaunchKernelGGL((attn_softmax_fwd_kernel<float, CAUSAL>), grid, dim3(256), 0, s, (const float*)S, mask,
+                       (float*)P, (float*)Pd, nh, L, Lp, scale, dropout_p, (uint64_t)seed);
+  VCG_LAUNCH_CHECK();
+  return VCG_OK;
+}
+
+VCG_API int vcg_attn_softmax_fwd(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh,
+                                 int L, int Lp, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
+  return attn_softmax_fwd<false>(dtype, S, mask, P, Pd, B, nh, L, Lp, scale, dropout_p, seed, s);
+}
+
+// flags: VCG_ATTN_CAUSAL
+VCG_API int vcg_attn_softmax_fwd_ex(int dtype, const void* S, const long long* mask, void* P, void* Pd, int B, int nh,
+                                    int L, int Lp, float scale, float dropout_p, unsigned long long seed, int flags,
+                                    hipStream_t s) {
+  VCG_REQUIRE((flags & ~VCG_ATTN_CAUSAL) == 0, "unknown flags");
+  if (flags & VCG_ATTN_CAUSAL)
+    return attn_softmax_fwd<true>(dtype, S, mask, P, Pd, B, nh, L, Lp, scale, dropout_p, seed, s);
+  return attn_softmax_fwd<false>(dtype, S, mask, P, Pd, B, nh, L, Lp, scale, dropout_p, seed, s);
+}
+
+template <bool CAUSAL>
+static int attn_softmax_bwd(int dtype, const void* dPd, const void* P, void* dS, int Z, int L, int Lp, float scale,
+                            float dropout_p, unsigned long long seed, hipStream_t s) {
+  VCG_REQUIRE(L <= 512 && Lp >= L && Lp % 2 == 0 && Lp <= 512, "L must be <= 512, Lp even");
+  dim3 grid((L + 3) / 4, Z);
+  if (dtype == VCG_BF16)
+    hipLaunchKernelGGL((attn_softmax_bwd_kernel<bf16_t, CAUSAL>), grid, dim3(256), 0, s, (const bf16_t*)dPd,
+                       (const bf16_t*)P, (bf16_t*)dS, L, Lp, scale, dropout_p, (uint64_t)seed, Z);
+  else
+    hipLaunchKernelGGL((attn_softmax_bwd_kernel<float, CAUSAL>), grid, dim3(256), 0, s, (const float*)dPd,
+                       (const float*)P, (float*)dS, L, Lp, scale, dropout_p, (uint64_t)seed, Z);
   VCG_LAUNCH_CHECK();
   return VCG_OK;
 }
 
 VCG_API int vcg_attn_softmax_bwd(int dtype, const void* dPd, const void* P, void* dS, int Z, int L, int Lp, float scale,
                                  float dropout_p, unsigned long long seed, hipStream_t s) {
-  VCG_REQUIRE(L <= 512 && Lp >= L && Lp % 2 == 0 && Lp <= 512, "L must be <= 512, Lp even");
-  dim3 grid((L + 3) / 4, Z);
-  if (dtype == VCG_BF16)
-    hipLaunchKernelGGL(attn_softmax_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dPd, (const bf16_t*)P,
-                       (bf16_t*)dS, L, Lp, scale, dropout_p, (uint64_t)seed, Z);
-  else
-    hipLaunchKernelGGL(attn_softmax_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dPd, (const float*)P,
-                       (float*)dS, L, Lp, scale, dropout_p, (uint64_t)seed, Z);
-  VCG_LAUNCH_CHECK();
-  return VCG_OK;
+  return attn_softmax_bwd<false>(dtype, dPd, P, dS, Z, L, Lp, scale, dropout_p, seed, s);
+}
+
+// flags: VCG_ATTN_CAUSAL
+VCG_API int vcg_attn_softmax_bwd_ex(int dtype, const void* dPd, const void* P, void* dS, int Z, int L, int Lp,
+                                    float scale, float dropout_p, unsigned long long seed, int flags, hipStream_t s) {
+  VCG_REQUIRE((flags & ~VCG_ATTN_CAUSAL) == 0, "unknown flags");
+  if (flags & VCG_ATTN_CAUSAL) return attn_softmax_bwd<true>(dtype, dPd, P, dS, Z, L, Lp, scale, dropout_p, seed, s);
+  return attn_softmax_bwd<false>(dtype, dPd, P, dS, Z, L, Lp, scale, dropout_p, seed, s);
 }
 
 VCG_API int vcg_tanh_bwd(int dtype, const void* dy, const void* t, void* dx, long long n, hipStream_t s) {

@@ -28,6 +28,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------ forward
 // 4 waves; wave w owns queries 32 w .. 32 w + 31. S^T = K Q^T (A = K rows from LDS, B = Q rows from HBM), the
 // softmax over the lane's 32 keys and the 4 lane groups, O^T = V^T Pd^T (A = V^T from LDS, B = Pd from registers).
+// CAUSAL (bert_attn_steps.h, the causal rule): the 16 x 16 score tiles and the PV k-steps past the wave's last query
+// are skipped, every element pays the key <= query compare (the whole row is unrolled in registers here).
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __restrict__ qkv,
                                                             const long long* __restrict__ mask,
                                                             bf16_t* __restrict__ ctx, float2* __restrict__ stats,
@@ -50,7 +53,8 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
   if (32 * w >= L) return;  // every query of this wave is past the end (no barrier follows)
 
   f32x4 sacc[2][8];  // lane holds S^T[key 16 kt + 4 g + r][query 32 w + 16 qt + i]
-  key_tiles<8>(sacc, Ks, 0, L, qf, g, i);
+  const bool skip = CAUSAL && causal_skip(mask, hd.row0, L);
+  key_tiles<8, CAUSAL>(sacc, Ks, 0, L, qf, g, i, skip ? 32 * w : NOSKIP);
   const uint32_t vb = key_bits<8>(kval, 0, g);
   const float rs = p > 0.f ? 1.f / (1.f - p) : 1.f;
   s16x8 pf[2][4];
@@ -62,7 +66,8 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
     for (int kt = 0; kt < 8; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = ((vb >> (4 * kt + r)) & 1u) ? sacc[qt][kt][r] * scale : -INFINITY;
+        const bool vis = visible<CAUSAL>((vb >> (4 * kt + r)) & 1u, 16 * kt + 4 * g + r, q);
+        const float v = vis ? sacc[qt][kt][r] * scale : -INFINITY;
         sacc[qt][kt][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.f / sum;
     if (g == 0 && q < L) stats[hd.so + q] = make_float2(mx, inv);
-    dropout_frags(pf[qt], sacc[qt], q < L, hd.drop_row(q), inv, rs, p, seed, g);
+    dropout_frags(pf[qt], sacc[qt], q < L, hd.drop_row(q), inv, rs, p, seed, g, skip ? 32 * w + 32 : NOSKIP);
   }
 
   f32x4 oacc[4][2];  // lane holds O^T[d 16 dt + 4 g + r][query 32 w + 16 qt + i]
@@ -92,7 +97,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) oacc[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  pv_step(oacc, Vt, pf, L, g, i);
+  pv_step(oacc, Vt, pf, skip ? min(L, 32 * w + 32) : L, g, i);
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = 32 * w + 16 * qt + i;
@@ -104,6 +109,9 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const bf16_t* __rest
 // 4 waves; wave w owns keys 32 w .. 32 w + 31 for S, dPd, dV and dK (A = Q / dO rows, Q^T / dO^T from LDS, B = the
 // wave's K / V rows from HBM, and its P / dS fragments from registers), then queries 32 w .. 32 w + 31 for dQ
 // (A = K^T from LDS, B = dS rows from the LDS copy every wave wrote). The forward's ctx is not read.
+// CAUSAL: the score tiles, the dropout hashes and the dV / dK k-steps of queries before the wave's first key, and the
+// dQ k-steps of keys past the wave's last query, are skipped (their P, dP and dS are exact zeros).
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __restrict__ qkv,
                                                             const bf16_t* __restrict__ dctx,
                                                             const long long* __restrict__ mask,
@@ -141,8 +149,9 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
   // so its dS entries -- read by every wave's dQ -- are exact zeros)
   const bool wkeys = 32 * w < L;
   f32x4 sacc[8][2], pacc[8][2];  // lane holds S / dPd [query 16 qt + 4 g + r][key 32 w + 16 kt + i]
-  query_tiles<8>(sacc, Qs, 0, wkeys ? L : 0, kf, g, i);
-  query_tiles<8>(pacc, dOs, 0, wkeys ? L : 0, vf, g, i);
+  const bool skip = CAUSAL && causal_skip(mask, hd.row0, L);
+  query_tiles<8, CAUSAL>(sacc, Qs, 0, wkeys ? L : 0, kf, g, i, skip ? 32 * w : -NOSKIP);
+  query_tiles<8, CAUSAL>(pacc, dOs, 0, wkeys ? L : 0, vf, g, i, skip ? 32 * w : -NOSKIP);
   const float rs = p > 0.f ? 1.f / (1.f - p) : 1.f;
   bool kv[2];
   int keyi[2];
@@ -153,30 +162,34 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
   }
   uint64_t keepb = 0;  // bit 8 qt + 2 r + kt: element (query 16 qt + 4 g + r, key keyi[kt]) kept by dropout
 #pragma unroll
-  for (int qt = 0; qt < 8; ++qt)
+  for (int qt = 0; qt < 8; ++qt) {
+    const bool dead = CAUSAL && skip && 16 * qt + 15 < 32 * w;  // (wave-uniform: every key of the wave is in the future)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = 16 * qt + 4 * g + r;
       const float2 mi = st[q];
       const uint64_t rowi = hd.drop_row(q);
       float part = 0.f;
+      if (!dead) {
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        const int key = keyi[kt];
-        const float P = attn_prob(sacc[qt][kt][r], scale, mi, kv[kt], key < L, q < L);
-        const bool keep = q < L && key < L && dropout_keep(seed, rowi + key, p);
-        const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
-        keepb |= keep ? (1ull << (8 * qt + 2 * r + kt)) : 0ull;
-        sacc[qt][kt][r] = P;
-        pacc[qt][kt][r] = dP;
-        part = fmaf(P, dP, part);
+        for (int kt = 0; kt < 2; ++kt) {
+          const int key = keyi[kt];
+          const float P = attn_prob(sacc[qt][kt][r], scale, mi, visible<CAUSAL>(kv[kt], key, q), key < L, q < L);
+          const bool keep = q < L && key < L && dropout_keep(seed, rowi + key, p);
+          const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
+          keepb |= keep ? (1ull << (8 * qt + 2 * r + kt)) : 0ull;
+          sacc[qt][kt][r] = P;
+          pacc[qt][kt][r] = dP;
+          part = fmaf(P, dP, part);
+        }
+        part += __shfl_xor(part, 1, 64);
+        part += __shfl_xor(part, 2, 64);
+        part += __shfl_xor(part, 4, 64);
+        part += __shfl_xor(part, 8, 64);
       }
-      part += __shfl_xor(part, 1, 64);
-      part += __shfl_xor(part, 2, 64);
-      part += __shfl_xor(part, 4, 64);
-      part += __shfl_xor(part, 8, 64);
       if (i == 0) Dp[w * LT + q] = part;
     }
+  }
   __syncthreads();  // Dp complete
 #pragma unroll
   for (int qt = 0; qt < 8; ++qt)
@@ -187,7 +200,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         const float P = sacc[qt][kt][r];
-        const float dS = scale * P * (pacc[qt][kt][r] - D);
+        const float dS = causal_ds<CAUSAL>(scale * P * (pacc[qt][kt][r] - D), keyi[kt], q);
         sacc[qt][kt][r] = ((keepb >> (8 * qt + 2 * r + kt)) & 1ull) ? P * rs : 0.f;  // Pd
         pacc[qt][kt][r] = dS;
         dSm[q * TP + keyi[kt]] = f2bf(dS);
@@ -202,7 +215,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < 4; ++s)
-    if (wkeys && 32 * s < L)
+    if (wkeys && 32 * s < L && !(skip && s < w))
       dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], dOt, Qt, 32 * s, g, i);
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
@@ -223,7 +236,8 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kernel(const bf16_t* __rest
     for (int qt = 0; qt < 2; ++qt) dq[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    if (32 * w >= L || 32 * s >= L) continue;  // (the wave's queries / this step's keys past the end)
+    if (32 * w >= L || 32 * s >= L || (skip && s > w)) continue;  // (the wave's queries / this step's keys past the
+                                                                     // end, or keys all in the wave's future)
     s16x8 sbq[2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt)
@@ -274,19 +288,35 @@ VCG_API long long vcg_bert_attn_stats_bytes(int B, int nh, int L) {
 // them; Lmax > 128: the tiled kernels of bert_attn_long.hip), mask the key flags of those rows (NULL: every row is a
 // key); stats and the dropout counters keep the padded [B][nh][Lmax] index space, so a sequence whose kept rows are a
 // prefix of its padded rows gets the padded result. seq NULL: padded, sequence b at rows b Lmax .. b Lmax + Lmax - 1.
-VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
-                                     int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
-                                     unsigned long long seed, hipStream_t s) {
+// flags: VCG_ATTN_CAUSAL (bert_attn_steps.h, the causal rule); 0 is vcg_bert_attn_fwd_varlen.
+VCG_API int vcg_bert_attn_fwd_ex(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
+                                 int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
+                                 unsigned long long seed, int flags, hipStream_t s) {
+  if (flags & ~VCG_ATTN_CAUSAL) {
+    set_error("vcg_bert_attn_fwd: unknown flags");
+    return VCG_ERR_INVALID;
+  }
+  const bool causal = (flags & VCG_ATTN_CAUSAL) != 0;
   if (B == 0 || Lmax == 0) return VCG_OK;
   int nT;
   const int rc = attn_check("vcg_bert_attn_fwd", qkv, ctx, stats, B, nh, Lmax, Lp, &nT);
   if (rc != VCG_OK) return rc;
   if (Lmax > LT)
-    return bert_attn_long_fwd(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, nT, scale, dropout_p, seed, s);
-  hipLaunchKernelGGL(bert_attn_fwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, mask, (bf16_t*)ctx,
-                     (float2*)stats, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
+    return bert_attn_long_fwd(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, nT, scale, dropout_p, seed, causal, s);
+  if (causal)
+    hipLaunchKernelGGL(bert_attn_fwd_kernel<true>, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, mask,
+                       (bf16_t*)ctx, (float2*)stats, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
+  else
+    hipLaunchKernelGGL(bert_attn_fwd_kernel<false>, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, mask,
+                       (bf16_t*)ctx, (float2*)stats, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
+}
+
+VCG_API int vcg_bert_attn_fwd_varlen(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats,
+                                     int B, int nh, int Lmax, int Lp, float scale, float dropout_p,
+                                     unsigned long long seed, hipStream_t s) {
+  return vcg_bert_attn_fwd_ex(qkv, mask, seq, ctx, stats, B, nh, Lmax, Lp, scale, dropout_p, seed, 0, s);
 }
 
 VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx, void* stats, int B, int nh, int L,
@@ -294,9 +324,14 @@ VCG_API int vcg_bert_attn_fwd(const void* qkv, const long long* mask, void* ctx,
   return vcg_bert_attn_fwd_varlen(qkv, mask, nullptr, ctx, stats, B, nh, L, Lp, scale, dropout_p, seed, s);
 }
 
-VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq,
-                                     const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale,
-                                     float dropout_p, unsigned long long seed, hipStream_t s) {
+VCG_API int vcg_bert_attn_bwd_ex(const void* qkv, const void* dctx, const long long* mask, const int* seq,
+                                 const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale,
+                                 float dropout_p, unsigned long long seed, int flags, hipStream_t s) {
+  if (flags & ~VCG_ATTN_CAUSAL) {
+    set_error("vcg_bert_attn_bwd: unknown flags");
+    return VCG_ERR_INVALID;
+  }
+  const bool causal = (flags & VCG_ATTN_CAUSAL) != 0;
   if (B == 0 || Lmax == 0) return VCG_OK;
   if (!dctx) {
     set_error("vcg_bert_attn_bwd: invalid arguments");
@@ -307,11 +342,23 @@ VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const lo
   if (rc != VCG_OK) return rc;
   if (Lmax > LT)  // (the tiled backward keeps its D vector in the stats buffer's tail)
     return bert_attn_long_bwd(qkv, dctx, mask, seq, const_cast<void*>(stats), dqkv, B, nh, Lmax, Lp, nT, scale,
-                              dropout_p, seed, s);
-  hipLaunchKernelGGL(bert_attn_bwd_kernel, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, mask,
-                     (const float2*)stats, (bf16_t*)dqkv, seq, nh, Lmax, Lp, scale, dropout_p, (uint64_t)seed);
+                              dropout_p, seed, causal, s);
+  if (causal)
+    hipLaunchKernelGGL(bert_attn_bwd_kernel<true>, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv,
+                       (const bf16_t*)dctx, mask, (const float2*)stats, (bf16_t*)dqkv, seq, nh, Lmax, Lp, scale,
+                       dropout_p, (uint64_t)seed);
+  else
+    hipLaunchKernelGGL(bert_attn_bwd_kernel<false>, dim3(B * nh), dim3(256), 0, s, (const bf16_t*)qkv,
+                       (const bf16_t*)dctx, mask, (const float2*)stats, (bf16_t*)dqkv, seq, nh, Lmax, Lp, scale,
+                       dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
+}
+
+VCG_API int vcg_bert_attn_bwd_varlen(const void* qkv, const void* dctx, const long long* mask, const int* seq,
+                                     const void* stats, void* dqkv, int B, int nh, int Lmax, int Lp, float scale,
+                                     float dropout_p, unsigned long long seed, hipStream_t s) {
+  return vcg_bert_attn_bwd_ex(qkv, dctx, mask, seq, stats, dqkv, B, nh, Lmax, Lp, scale, dropout_p, seed, 0, s);
 }
 
 VCG_API int vcg_bert_attn_bwd(const void* qkv, const void* dctx, const void* ctx, const long long* mask,

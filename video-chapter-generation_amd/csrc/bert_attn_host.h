@@ -15,11 +15,13 @@ inline long long stats_rows(int B, int nh, int L) { return (long long)B * nh * s
 
 }  // namespace attn
 
-// 128 < Lmax <= 512, nT = stats_tiles(Lmax); the other arguments are vcg_bert_attn_fwd/bwd_varlen's, already checked
+// 128 < Lmax <= 512, nT = stats_tiles(Lmax), causal: VCG_ATTN_CAUSAL was given; the other arguments are
+// vcg_bert_attn_fwd/bwd_varlen's, already checked
 int bert_attn_long_fwd(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats, int B, int nh,
-                       int Lmax, int Lp, int nT, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
+                       int Lmax, int Lp, int nT, float scale, float dropout_p, unsigned long long seed, bool causal,
+                       hipStream_t s);
 int bert_attn_long_bwd(const void* qkv, const void* dctx, const long long* mask, const int* seq, void* stats,
                        void* dqkv, int B, int nh, int Lmax, int Lp, int nT, float scale, float dropout_p,
-                       unsigned long long seed, hipStream_t s);
+                       unsigned long long seed, bool causal, hipStream_t s);
 
 }  // namespace vcg

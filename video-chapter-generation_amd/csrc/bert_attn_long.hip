@@ -37,6 +37,13 @@
 //   dkv: LDS 67.5 KiB (Q, dO row-major 32 + Q^T, dO^T 34 + stats, D 1.5); a tile's queries in two halves of 64, so S 32
 //        + dPd 32 + dV^T, dK^T 64 accumulators; 256 VGPRs, no spill
 // The tiles are single-buffered (two barriers per tile); at L <= 512 a sweep is at most 4 tiles.
+//
+// CAUSAL instantiations (bert_attn_steps.h, the causal rule): the forward and dq visit key tiles up to their own query
+// tile only, dkv query tiles from its own key tile on; inside the diagonal tile the 16 x 16 MFMA tiles, the 64-wide
+// halves and the PV / dQ / dV / dK k-steps above the diagonal are skipped too, and only there does the key <= query
+// compare decide anything. A query without a visible key exists iff the sequence's first key is masked: then nothing
+// is skipped (causal_skip) and the forward finds the first valid key kfirst once per workgroup -- query q < kfirst has
+// no visible key and is uniform over all L keys (score 0 for every key in range, saved as row max = -inf).
 #include <type_traits>
 
 #include "bert_attn_host.h"
@@ -48,6 +55,7 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------ forward
 // blockIdx.x = z * nT + query tile; wave w owns queries q0 + 32 w .. + 31
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t* __restrict__ qkv,
                                                                  const long long* __restrict__ mask,
                                                                  bf16_t* __restrict__ ctx, float2* __restrict__ stats,
@@ -62,10 +70,30 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
   if (q0 >= L) return;  // (a packed sequence that ends before this query tile; block-uniform, before any barrier)
   const bf16_t* base = qkv + hd.qo;  // Q of (b, h); K at + H, V at + 2 H
 
-  int anyk = mask == nullptr;
-  if (mask)
-    for (int k = tid; k < L; k += 256) anyk |= mask[(long long)hd.row0 + k] != 0;
-  const bool none = !__syncthreads_or(anyk);  // no valid key in the whole sequence: uniform attention
+  bool none;       // no valid key in the whole sequence: uniform attention
+  int kfirst = 0;  // CAUSAL: the first valid key (L: none); queries before it have no visible key
+  if constexpr (CAUSAL) {
+    __shared__ int kfs;
+    if (tid == 0) kfs = L;
+    __syncthreads();
+    if (mask) {
+      int kf = L;
+      for (int k = tid; k < L; k += 256)
+        if (mask[(long long)hd.row0 + k] != 0) kf = min(kf, k);
+      if (kf < L) atomicMin(&kfs, kf);
+    } else if (tid == 0) {
+      kfs = 0;
+    }
+    __syncthreads();
+    kfirst = kfs;
+    none = false;  // (decided per query below)
+  } else {
+    int anyk = mask == nullptr;
+    if (mask)
+      for (int k = tid; k < L; k += 256) anyk |= mask[(long long)hd.row0 + k] != 0;
+    none = !__syncthreads_or(anyk);
+  }
+  const bool skip = CAUSAL && kfirst == 0;  // (= causal_skip: the first key is valid)
 
   s16x8 qf[2][2];
   load_frags(qf, base, ld, q0 + 32 * w, L, g, i);
@@ -78,15 +106,20 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) oacc[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int k0 = 0; k0 < L; k0 += LT) {
+  const int kend = skip ? min(L, q0 + LT) : L;  // (causal: the key tiles past the query tile are not visited)
+  for (int k0 = 0; k0 < kend; k0 += LT) {
     const int Lt = L - k0;  // keys of this tile (>= 128: a full tile)
     load_rm(base + (long long)k0 * ld + H, ld, Lt, Ks, tid);
     load_transpose(base + (long long)k0 * ld + 2 * H, ld, Lt, Vt, nullptr, tid);
     load_key_flags(kval, none ? nullptr : mask, (long long)hd.row0 + k0, Lt, tid);
     __syncthreads();
-    if (wact) {
+    // one key tile; MK: the causal rule acts inside it -- the diagonal tile, or any tile of a sequence whose first key
+    // is masked (!skip). A tile below the diagonal (MK false) is the non-causal tile body: every key before every query
+    auto tile = [&](auto MASK) {
+      constexpr bool MK = decltype(MASK)::value;
+      const int qlo = MK && skip ? q0 + 32 * w - k0 : NOSKIP;  // the wave's first query in the tile's key coordinates
       f32x4 sacc[2][8];  // lane holds S^T[key k0 + 16 kt + 4 g + r][query q0 + 32 w + 16 qt + i]
-      key_tiles<8>(sacc, Ks, 0, Lt, qf, g, i);
+      key_tiles<8, MK>(sacc, Ks, 0, Lt, qf, g, i, qlo);
       const uint32_t vb = key_bits<8>(kval, 0, g);
       s16x8 pf[2][4];
 #pragma unroll
@@ -97,7 +130,14 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
         for (int kt = 0; kt < 8; ++kt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float v = ((vb >> (4 * kt + r)) & 1u) ? (none ? 0.f : sacc[qt][kt][r] * scale) : -INFINITY;
+            float v;
+            if constexpr (MK) {
+              const int kl = 16 * kt + 4 * g + r;
+              if (q < kfirst) v = kl < Lt ? 0.f : -INFINITY;  // no visible key: every key in range, score 0
+              else v = visible<true>((vb >> (4 * kt + r)) & 1u, k0 + kl, q) ? sacc[qt][kt][r] * scale : -INFINITY;
+            } else {
+              v = ((vb >> (4 * kt + r)) & 1u) ? (none ? 0.f : sacc[qt][kt][r] * scale) : -INFINITY;
+            }
             sacc[qt][kt][r] = v;
             mx = fmaxf(mx, v);
           }
@@ -123,9 +163,14 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) oacc[dt][qt][r] *= alpha;
-        dropout_frags(pf[qt], sacc[qt], q < L, hd.drop_row(q) + k0, 1.f, rs, p, seed, g);  // (1 / l: at the end)
+        dropout_frags(pf[qt], sacc[qt], q < L, hd.drop_row(q) + k0, 1.f, rs, p, seed, g,
+                      MK && skip ? qlo + 32 : NOSKIP);  // (1 / l: at the end)
       }
-      pv_step(oacc, Vt, pf, Lt, g, i);
+      pv_step(oacc, Vt, pf, MK && skip ? min(Lt, qlo + 32) : Lt, g, i);
+    };
+    if (wact) {
+      if (CAUSAL && (!skip || k0 == q0)) tile(std::true_type{});
+      else tile(std::false_type{});
     }
     __syncthreads();  // every wave is done with this tile before the next one overwrites it
   }
@@ -135,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
     const int q = q0 + 32 * w + 16 * qt + i;
     if (q < L) {
       const float inv = 1.f / l[qt];
-      if (g == 0) stats[hd.so + q] = make_float2(none ? -INFINITY : m[qt], inv);
+      if (g == 0) stats[hd.so + q] = make_float2((none || (CAUSAL && q < kfirst)) ? -INFINITY : m[qt], inv);
       store_row64(ctx + hd.co + (long long)q * H + 4 * g, oacc, qt, inv);
     }
   }
@@ -144,6 +189,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
 // ------------------------------------------------------------------------------------------------ backward: D, dQ
 // blockIdx.x = z * nT + query tile; wave w owns queries q0 + 32 w .. + 31. S^T = K Q^T and dPd^T = V dO^T (A = K / V
 // rows from LDS, B = the wave's Q / dO rows from HBM), dQ^T = K^T dS^T (A = K^T from LDS, B = dS from registers).
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t* __restrict__ qkv,
                                                                 const bf16_t* __restrict__ dctx,
                                                                 const long long* __restrict__ mask,
@@ -180,20 +226,25 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) dq[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  const bool skip = CAUSAL && causal_skip(mask, hd.row0, L);
+  const int kend = skip ? min(L, q0 + LT) : L;  // (causal: the key tiles past the query tile are not visited)
   for (int sweep = 0; sweep < 2; ++sweep) {  // 0: D; 1: dS and dQ
-    for (int k0 = 0; k0 < L; k0 += LT) {
+    for (int k0 = 0; k0 < kend; k0 += LT) {
       const int Lt = L - k0;
+      const int qlo = skip ? q0 + 32 * w - k0 : NOSKIP;  // the wave's first query in the tile's key coordinates
       if (sweep == 0) load_rm(base + (long long)k0 * ld + H, ld, Lt, Ks, tid);
       else load_transpose(base + (long long)k0 * ld + H, ld, Lt, Kt, Ks, tid);
       load_rm(base + (long long)k0 * ld + 2 * H, ld, Lt, Vs, tid);
       load_key_flags(kval, mask, (long long)hd.row0 + k0, Lt, tid);
       __syncthreads();
-      // one half (64 keys) of the tile; SW = the sweep, a compile-time constant inside
-      auto half = [&](auto SW, int kh) {
+      // one half (64 keys) of the tile; SW = the sweep, MASK = the causal rule acts inside the tile (the diagonal tile,
+      // or any tile of a sequence whose first key is masked; otherwise the non-causal body), compile-time constants
+      auto half = [&](auto SW, auto MASK, int kh) {
         constexpr int sw = decltype(SW)::value;
+        constexpr bool MK = decltype(MASK)::value;
         f32x4 sacc[2][4], pacc[2][4];  // lane holds S^T / dPd^T [key k0 + kh + 16 kt + 4 g + r][query q0 + 32 w + 16 qt + i]
-        key_tiles<4>(sacc, Ks, kh, Lt, qf, g, i);
-        key_tiles<4>(pacc, Vs, kh, Lt, df, g, i);
+        key_tiles<4, MK>(sacc, Ks, kh, Lt, qf, g, i, qlo);
+        key_tiles<4, MK>(pacc, Vs, kh, Lt, df, g, i, qlo);
         const uint32_t vb = key_bits<4>(kval, kh, g);
         // the lane's 32 dropout decisions of this half (bit 16 qt + 4 kt + r): hashed in sweep 0, reread in sweep 1
         uint32_t* kw = keepw + ((k0 + kh) >> 6) * 256 + tid;
@@ -208,7 +259,8 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int kl = kh + 16 * kt + 4 * g + r;
-              const float P = attn_prob(sacc[qt][kt][r], scale, mi[qt], (vb >> (4 * kt + r)) & 1u, kl < Lt, q < L);
+              const float P = attn_prob(sacc[qt][kt][r], scale, mi[qt],
+                                        visible<MK>((vb >> (4 * kt + r)) & 1u, k0 + kl, q), kl < Lt, q < L);
               const uint32_t bit = 1u << (16 * qt + 4 * kt + r);
               bool keep;
               if constexpr (sw == 0) {
@@ -219,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
               }
               const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
               if constexpr (sw == 0) part = fmaf(P, dP, part);
-              else sacc[qt][kt][r] = scale * P * (dP - D[qt]);  // dS
+              else sacc[qt][kt][r] = causal_ds<MK>(scale * P * (dP - D[qt]), k0 + kl, q);  // dS
             }
           if constexpr (sw == 0) D[qt] += part;
         }
@@ -227,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
         if constexpr (sw == 1) {
 #pragma unroll
           for (int s = 0; s < 2; ++s)
-            if (kh + 32 * s < Lt) {
+            if (kh + 32 * s < Lt && (!MK || kh + 32 * s <= qlo + 31)) {
               s16x8 sf[2];
 #pragma unroll
               for (int qt = 0; qt < 2; ++qt) sf[qt] = pack8(sacc[qt][2 * s], sacc[qt][2 * s + 1]);
@@ -243,8 +295,14 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
       };
 #pragma unroll 1
       for (int kh = 0; kh < (wact ? LT : 0) && kh < Lt; kh += 64) {  // (a wave past the end only loads and syncs)
-        if (sweep == 0) half(std::integral_constant<int, 0>{}, kh);
-        else half(std::integral_constant<int, 1>{}, kh);
+        if (CAUSAL && kh > qlo + 31) break;  // (the half lies past the wave's last query)
+        if (CAUSAL && (!skip || k0 == q0)) {
+          if (sweep == 0) half(std::integral_constant<int, 0>{}, std::true_type{}, kh);
+          else half(std::integral_constant<int, 1>{}, std::true_type{}, kh);
+        } else {
+          if (sweep == 0) half(std::integral_constant<int, 0>{}, std::false_type{}, kh);
+          else half(std::integral_constant<int, 1>{}, std::false_type{}, kh);
+        }
       }
       __syncthreads();
     }
@@ -269,6 +327,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
 // blockIdx.x = z * nT + key tile; wave w owns keys k0 + 32 w .. + 31 (A = Q / dO rows, Q^T / dO^T from LDS, B = the
 // wave's K / V rows from HBM and its Pd / dS fragments from registers).
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t* __restrict__ qkv,
                                                                  const bf16_t* __restrict__ dctx,
                                                                  const long long* __restrict__ mask,
@@ -308,8 +367,13 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int q0 = 0; q0 < L; q0 += LT) {
+  const bool skip = CAUSAL && causal_skip(mask, hd.row0, L);
+  // one query tile; MASK = the causal rule acts inside it (the diagonal tile, or any tile of a sequence whose first
+  // key is masked; otherwise the non-causal body: every key of the workgroup lies before every query of the tile)
+  auto qtile = [&](auto MASK, int q0) {
+    constexpr bool MK = decltype(MASK)::value;
     const int Lq = L - q0;
+    const int klo = skip ? k0 + 32 * w - q0 : -NOSKIP;  // the wave's first key in the tile's query coordinates
     load_transpose(base + (long long)q0 * ld, ld, Lq, Qt, Qs, tid);
     load_transpose(dob + (long long)q0 * H, H, Lq, dOt, dOs, tid);
     if (tid < LT) {
@@ -319,9 +383,10 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
     __syncthreads();
 #pragma unroll 1
     for (int qh = 0; qh < (wact ? LT : 0) && qh < Lq; qh += 64) {  // the tile's queries in two halves of 64
+      if (MK && qh + 63 < klo) continue;  // (the half lies before the wave's first key)
       f32x4 sacc[4][2], pacc[4][2];  // lane holds S / dPd [query q0 + qh + 16 qt + 4 g + r][key k0 + 32 w + 16 kt + i]
-      query_tiles<4>(sacc, Qs, qh, Lq, kf, g, i);
-      query_tiles<4>(pacc, dOs, qh, Lq, vf, g, i);
+      query_tiles<4, MK>(sacc, Qs, qh, Lq, kf, g, i, klo);
+      query_tiles<4, MK>(pacc, dOs, qh, Lq, vf, g, i, klo);
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt)
 #pragma unroll
@@ -333,21 +398,30 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt) {
             const int key = keyi[kt];
-            const float P = attn_prob(sacc[qt][kt][r], scale, mi, kv[kt], key < L, ql < Lq);
+            const float P = attn_prob(sacc[qt][kt][r], scale, mi, visible<MK>(kv[kt], key, q0 + ql), key < L, ql < Lq);
             const bool keep = ql < Lq && key < L && dropout_keep(seed, rowi + key, p);
             const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
             sacc[qt][kt][r] = keep ? P * rs : 0.f;    // Pd
-            pacc[qt][kt][r] = scale * P * (dP - D);   // dS
+            pacc[qt][kt][r] = causal_ds<MK>(scale * P * (dP - D), key, q0 + ql);   // dS
           }
         }
       // dV^T += dO^T Pd, dK^T += Q^T dS (k-step s: queries {32 s + 4 g + r, 32 s + 16 + 4 g + r} of the half)
 #pragma unroll
       for (int s = 0; s < 2; ++s)
-        if (qh + 32 * s < Lq)
+        if (qh + 32 * s < Lq && (!MK || qh + 32 * s + 31 >= klo))
           dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], dOt, Qt, qh + 32 * s, g, i);
     }
     __syncthreads();
+  };
+  // (causal: the query tiles before the key tile are not visited; the masked body runs on the diagonal tile only,
+  // or on every tile where nothing may be skipped)
+  int q0 = skip ? k0 : 0;
+  if constexpr (CAUSAL) {
+#pragma unroll 1
+    for (const int qe = skip ? min(L, k0 + LT) : L; q0 < qe; q0 += LT) qtile(std::true_type{}, q0);
   }
+#pragma unroll 1
+  for (; q0 < L; q0 += LT) qtile(std::false_type{}, q0);
   if (!wact) return;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
@@ -365,26 +439,27 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
 namespace vcg {
 
 int bert_attn_long_fwd(const void* qkv, const long long* mask, const int* seq, void* ctx, void* stats, int B, int nh,
-                       int Lmax, int Lp, int nT, float scale, float dropout_p, unsigned long long seed,
+                       int Lmax, int Lp, int nT, float scale, float dropout_p, unsigned long long seed, bool causal,
                        hipStream_t s) {
-  hipLaunchKernelGGL(bert_attn_long_fwd_kernel, dim3(B * nh * nT), dim3(256), 0, s, (const bf16_t*)qkv, mask,
-                     (bf16_t*)ctx, (float2*)stats, seq, nh, Lmax, Lp, nT, scale, dropout_p, (uint64_t)seed);
+  hipLaunchKernelGGL(causal ? bert_attn_long_fwd_kernel<true> : bert_attn_long_fwd_kernel<false>, dim3(B * nh * nT),
+                     dim3(256), 0, s, (const bf16_t*)qkv, mask, (bf16_t*)ctx, (float2*)stats, seq, nh, Lmax, Lp, nT,
+                     scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
 }
 
 int bert_attn_long_bwd(const void* qkv, const void* dctx, const long long* mask, const int* seq, void* stats,
                        void* dqkv, int B, int nh, int Lmax, int Lp, int nT, float scale, float dropout_p,
-                       unsigned long long seed, hipStream_t s) {
+                       unsigned long long seed, bool causal, hipStream_t s) {
   const float2* st = (const float2*)stats;
   float* Dv = (float*)(st + stats_rows(B, nh, Lmax));
-  hipLaunchKernelGGL(bert_attn_long_dq_kernel, dim3(B * nh * nT), dim3(256), 0, s, (const bf16_t*)qkv,
-                     (const bf16_t*)dctx, mask, st, Dv, (bf16_t*)dqkv, seq, nh, Lmax, Lp, nT, scale, dropout_p,
-                     (uint64_t)seed);
+  hipLaunchKernelGGL(causal ? bert_attn_long_dq_kernel<true> : bert_attn_long_dq_kernel<false>, dim3(B * nh * nT),
+                     dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, mask, st, Dv, (bf16_t*)dqkv, seq, nh,
+                     Lmax, Lp, nT, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(bert_attn_long_dkv_kernel, dim3(B * nh * nT), dim3(256), 0, s, (const bf16_t*)qkv,
-                     (const bf16_t*)dctx, mask, st, (const float*)Dv, (bf16_t*)dqkv, seq, nh, Lmax, Lp, nT, scale,
-                     dropout_p, (uint64_t)seed);
+  hipLaunchKernelGGL(causal ? bert_attn_long_dkv_kernel<true> : bert_attn_long_dkv_kernel<false>, dim3(B * nh * nT),
+                     dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dctx, mask, st, (const float*)Dv,
+                     (bf16_t*)dqkv, seq, nh, Lmax, Lp, nT, scale, dropout_p, (uint64_t)seed);
   VCG_CHECK_HIP(hipGetLastError());
   return VCG_OK;
 }

@@ -85,6 +85,29 @@ struct Head {
   __device__ __forceinline__ uint64_t drop_row(int q) const { return ((uint64_t)z * Lmax + q) * (uint64_t)Lp; }
 };
 
+// ---------------------------------------------------------------------------------------------- causal rule
+// CAUSAL instantiations: key j is visible to query i iff j <= i and the key is valid (its mask entry set). A query
+// without any visible key keeps the no-key convention (attn_prob): uniform over all L keys in range, future ones
+// included -- which is what HF's OpenAIGPT computes for a fully masked sequence. Such a row exists iff the
+// sequence's first key is masked (every query sees key 0 otherwise), so that one block-uniform flag decides
+// whether tiles wholly above the diagonal may be skipped: skipping is what the NOSKIP bounds below turn off.
+template <bool CAUSAL>
+__device__ __forceinline__ bool visible(bool valid_key, int key, int q) {
+  return valid_key && (!CAUSAL || key <= q);
+}
+constexpr int NOSKIP = 1 << 20;  // a first-query / first-key bound under which no tile lies above the diagonal
+// may tiles wholly above the diagonal be skipped? (not when some query has no visible key: see above)
+__device__ __forceinline__ bool causal_skip(const long long* mask, long long row0, int L) {
+  return mask == nullptr || L <= 0 || mask[row0] != 0;
+}
+
+// the causal cut of dS: no gradient reaches a future key's score -- HF's `w * b + -1e4 (1 - b)` fill multiplies it by
+// b = 0. P is zero there anyway, except in a row without a visible key (uniform over all L keys: D still sums over all)
+template <bool CAUSAL>
+__device__ __forceinline__ float causal_ds(float dS, int key, int q) {
+  return (CAUSAL && key > q) ? 0.f : dS;
+}
+
 // ---------------------------------------------------------------------------------------------- loads
 // rows 0 .. 127 of a [nrows][ld] row-major source (rows >= nrows zero) -> the swizzled row-major tile rm[row][64]
 __device__ __forceinline__ void load_rm(const bf16_t* src, long long ld, int nrows, bf16_t* rm, int tid) {
@@ -139,22 +162,26 @@ __device__ __forceinline__ void load_frags(s16x8 (&f)[2][2], const bf16_t* src, 
 // ---------------------------------------------------------------------------------------------- key-major tiles
 // (the forwards and dq: a lane holds [key r0 + 16 kt + 4 g + r][query 16 qt + i of the wave's 32])
 // acc[qt][kt] = A B^T over the head dim: A = rows r0 + 16 kt .. + 15 of the swizzled LDS tile a (K for S^T, V for
-// dPd^T), B = the wave's Q / dO fragments; tiles whose rows start at or past nrows stay zero
-template <int NT>
+// dPd^T), B = the wave's Q / dO fragments; tiles whose rows start at or past nrows stay zero. CAUSAL: qlo is the wave's
+// first query in the tile's key coordinates (NOSKIP: no skipping); a 16 x 16 tile whose first key lies past its last
+// query (16 qt + 15 of the wave) is wholly above the diagonal and stays zero
+template <int NT, bool CAUSAL = false>
 __device__ __forceinline__ void key_tiles(f32x4 (&acc)[2][NT], const bf16_t* a, int r0, int nrows,
-                                          const s16x8 (&bf)[2][2], int g, int i) {
+                                          const s16x8 (&bf)[2][2], int g, int i, int qlo = NOSKIP) {
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) acc[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int kt = 0; kt < NT; ++kt)
-    if (r0 + 16 * kt < nrows) {
+    if (r0 + 16 * kt < nrows && (!CAUSAL || r0 + 16 * kt <= qlo + 31)) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const s16x8 af = frag_rm(a, r0 + 16 * kt + i, 4 * s + g);
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) acc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[qt][s], acc[qt][kt], 0, 0, 0);
+        for (int qt = 0; qt < 2; ++qt)
+          if (!CAUSAL || r0 + 16 * kt <= qlo + 16 * qt + 15)
+            acc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[qt][s], acc[qt][kt], 0, 0, 0);
       }
     }
 }
@@ -171,12 +198,17 @@ __device__ __forceinline__ uint32_t key_bits(const uint8_t* kval, int r0, int g)
 }
 
 // the forward's step from a query row's eight probability tiles e[kt] to the four B fragments of Pd = dropout(e * inv):
-// counter rowi + key (rowi: Head::drop_row(q) + the tile's first key), a row past the end (!row) all zero
+// counter rowi + key (rowi: Head::drop_row(q) + the tile's first key), a row past the end (!row) all zero. nk: the
+// k-steps from key nk on hold only zeros (the causal diagonal tile: keys past the wave's last query) and are not hashed
 __device__ __forceinline__ void dropout_frags(s16x8 (&pf)[4], const f32x4 (&e)[8], bool row, uint64_t rowi, float inv,
-                                              float rs, float p, uint64_t seed, int g) {
+                                              float rs, float p, uint64_t seed, int g, int nk = NOSKIP) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     f32x4 a, c;
+    if (32 * s >= nk) {  // (wave-uniform)
+      pf[s] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      continue;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int k0 = 32 * s + 4 * g + r, k1 = k0 + 16;
@@ -188,7 +220,8 @@ __device__ __forceinline__ void dropout_frags(s16x8 (&pf)[4], const f32x4 (&e)[8
   }
 }
 
-// O^T += V^T Pd^T over a tile's nkeys keys (A = V^T from LDS, B = Pd from registers; k-steps past the end skipped)
+// O^T += V^T Pd^T over a tile's nkeys keys (A = V^T from LDS, B = Pd from registers; k-steps past the end skipped --
+// the causal kernels pass the end of the wave's visible keys when that is sooner)
 __device__ __forceinline__ void pv_step(f32x4 (&oacc)[4][2], const bf16_t* Vt, const s16x8 (&pf)[2][4], int nkeys, int g,
                                         int i) {
 #pragma unroll
@@ -206,28 +239,33 @@ __device__ __forceinline__ void pv_step(f32x4 (&oacc)[4][2], const bf16_t* Vt, c
 // ---------------------------------------------------------------------------------------------- query-major tiles
 // (the L <= 128 backward and dkv: a lane holds [query 16 qt + 4 g + r][key 16 kt + i of the wave's 32])
 // acc[qt][kt] = A B^T over the head dim: A = rows r0 + 16 qt .. + 15 of the swizzled LDS tile a (Q for S, dO for dPd),
-// B = the wave's K / V fragments; tiles whose rows start at or past nrows stay zero
-template <int NT>
+// B = the wave's K / V fragments; tiles whose rows start at or past nrows stay zero. CAUSAL: klo is the wave's first
+// key in the tile's query coordinates (-NOSKIP: no skipping); a 16 x 16 tile whose last query lies before its first
+// key (16 kt of the wave) is wholly above the diagonal and stays zero
+template <int NT, bool CAUSAL = false>
 __device__ __forceinline__ void query_tiles(f32x4 (&acc)[NT][2], const bf16_t* a, int r0, int nrows,
-                                            const s16x8 (&bf)[2][2], int g, int i) {
+                                            const s16x8 (&bf)[2][2], int g, int i, int klo = -NOSKIP) {
 #pragma unroll
   for (int qt = 0; qt < NT; ++qt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) acc[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int qt = 0; qt < NT; ++qt)
-    if (r0 + 16 * qt < nrows) {
+    if (r0 + 16 * qt < nrows && (!CAUSAL || r0 + 16 * qt + 15 >= klo)) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const s16x8 af = frag_rm(a, r0 + 16 * qt + i, 4 * s + g);
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt) acc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[kt][s], acc[qt][kt], 0, 0, 0);
+        for (int kt = 0; kt < 2; ++kt)
+          if (!CAUSAL || r0 + 16 * qt + 15 >= klo + 16 * kt)
+            acc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[kt][s], acc[qt][kt], 0, 0, 0);
       }
     }
 }
 
 // The backward's P from a score and the saved (row max, 1 / row sum): a row without any key is saved with max = -inf
 // and 1 / sum = 1 / L and is uniform over the L keys in range, masked or not; otherwise a masked key has P = 0
+// (valid_key: the causal kernels pass visible<true>(...), so a future key counts as masked)
 __device__ __forceinline__ float attn_prob(float score, float scale, float2 mi, bool valid_key, bool key_in_range,
                                            bool row_in_range) {
   if (!row_in_range) return 0.f;

@@ -28,6 +28,7 @@ void census_add(const char* tag, long long M, long long N, long long K);
 
 enum vcg_dtype { VCG_F32 = 0, VCG_BF16 = 1 };
 enum { VCG_GRAD_F32 = 0x10 };  // vcg_ln_bwd / vcg_embed_ln_bwd dtype flag (include/vcg_hip.h)
+enum { VCG_ATTN_CAUSAL = 1 };  // vcg_bert_attn_*_ex / vcg_attn_softmax_fwd_ex flag (include/vcg_hip.h)
 enum vcg_status {
   VCG_OK = 0,
   VCG_ERR_INVALID = -1,
@@ -160,6 +161,25 @@ __device__ __forceinline__ float gelu_erf_fast(float x) { return 0.5f * x * (1.f
 __device__ __forceinline__ float gelu_erf_grad_fast(float x) {
   const float cdf = 0.5f * (1.f + erf_fast(x * 0.70710678118654752f));
   return fmaf(x * 0.39894228040143268f, __expf(-0.5f * x * x), cdf);
+}
+
+// The tanh form of GELU (transformers' NewGELUActivation, OpenAIGPT's afn): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x +
+// 0.044715 x^3), and its derivative 0.5 (1 + tanh u) + 0.5 x (1 - tanh^2 u) u'. The fast forms (bf16 epilogues) use
+// 0.5 (1 + tanh u) = sigmoid(2u) = 1 / (1 + exp(-2u)): one v_exp_f32 and one v_rcp_f32, relative error a few fp32
+// ulps in both tails (exp(-2u) -> inf gives 0, -> 0 gives 1), far below the bf16 rounding of the output.
+__device__ __forceinline__ float gelu_tanh_u(float x) { return 0.79788456080286536f * x * fmaf(0.044715f * x, x, 1.f); }
+__device__ __forceinline__ float gelu_tanh_du(float x) { return 0.79788456080286536f * fmaf(0.134145f * x, x, 1.f); }
+__device__ __forceinline__ float gelu_tanh(float x) { return 0.5f * x * (1.f + tanhf(gelu_tanh_u(x))); }
+__device__ __forceinline__ float gelu_tanh_grad(float x) {
+  const float t = tanhf(gelu_tanh_u(x));
+  return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * gelu_tanh_du(x);
+}
+__device__ __forceinline__ float gelu_tanh_fast(float x) {
+  return x * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * gelu_tanh_u(x)));
+}
+__device__ __forceinline__ float gelu_tanh_grad_fast(float x) {
+  const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-2.f * gelu_tanh_u(x)));  // 0.5 (1 + tanh u)
+  return fmaf(2.f * x * gelu_tanh_du(x), sg * (1.f - sg), sg);                  // 0.5 (1 - tanh^2 u) = 2 sg (1 - sg)
 }
 
 // Counter-based hash (splitmix64 finaliser), shared by dropout and the synthetic generator.

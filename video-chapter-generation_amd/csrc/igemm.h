@@ -14,7 +14,9 @@ enum { OP_DENSE_K = 0, OP_IM2COL = 1, OP_DGRAD = 2, OP_DENSE_MN = 3, OP_IM2COL_T
 // operands are DMA'd into an LDS ring several tiles ahead (igemm_fast.hip bwd_stream_body)
 enum { EPI_STORE = 0, EPI_STATS = 1, EPI_SPLITK = 2, EPI_BWD = 3, EPI_BWD_AFF = 4, EPI_STORE_AUX = 5,
        EPI_BWD_STREAM = 6 };
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_GELU_BWD = 4 };
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_GELU_BWD = 4, ACT_GELU_TANH = 5, ACT_GELU_TANH_BWD = 6 };
+// the two "multiply by GELU' of the residual" codes (the residual is the saved pre-activation, not an addend)
+__host__ __device__ __forceinline__ bool act_is_gelu_bwd(int act) { return act == ACT_GELU_BWD || act == ACT_GELU_TANH_BWD; }
 enum { ACT_FLAG_ROUND_PRE = 0x100 };  // = VCG_ACT_FLAG_ROUND_PRE (include/vcg_hip.h)
 enum { ACT_FLAG_WIDE = 0x200 };       // = VCG_ACT_FLAG_WIDE: run this GEMM on the wide-tile engine (igemm_wide.hip)
 enum { ACT_FLAG_F32_OUT = 0x400 };    // = VCG_ACT_FLAG_F32_OUT: fp32 residual and output (wide engine, bf16 operands)
@@ -147,6 +149,7 @@ __device__ __forceinline__ float apply_act(float v, int act, bool fast = false) 
   if (act == ACT_RELU) return fmaxf(v, 0.f);
   if (act == ACT_GELU) return fast ? gelu_erf_fast(v) : gelu_erf(v);
   if (act == ACT_TANH) return tanhf(v);
+  if (act == ACT_GELU_TANH) return fast ? gelu_tanh_fast(v) : gelu_tanh(v);
   return v;
 }
 
@@ -214,13 +217,16 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[BM / 32][BN / 32], co
         if (p.act == ACT_GELU_BWD) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] *= (sizeof(T) == 2 && p.fast_act) ? gelu_erf_grad_fast(rv[r]) : gelu_erf_grad(rv[r]);
+        } else if (p.act == ACT_GELU_TANH_BWD) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] *= (sizeof(T) == 2 && p.fast_act) ? gelu_tanh_grad_fast(rv[r]) : gelu_tanh_grad(rv[r]);
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += rv[r];
         }
       }
       if (p.aux) store4<T>(reinterpret_cast<T*>(p.aux) + (long long)m * p.ldc + n, v);
-      if (p.act != ACT_NONE && p.act != ACT_GELU_BWD) {
+      if (p.act != ACT_NONE && !act_is_gelu_bwd(p.act)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = apply_act(v[r], p.act, sizeof(T) == 2 && p.fast_act);
       }

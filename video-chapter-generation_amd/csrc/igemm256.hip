@@ -318,7 +318,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         float x = acc[i][j][r];
         if constexpr (EPI == EPI_STORE) {
           x = x * p.alpha + bv[r];
-          if (p.act != ACT_NONE && p.act != ACT_GELU_BWD) x = apply_act(x, p.act, p.fast_act);
+          if (p.act != ACT_NONE && !act_is_gelu_bwd(p.act)) x = apply_act(x, p.act, p.fast_act);
         }
         v[r] = x;
       }

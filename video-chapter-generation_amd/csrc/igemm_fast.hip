@@ -92,7 +92,7 @@ __device__ __forceinline__ void epilogue_staged(f32x4 (&acc)[4][BN / 32], const 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float t = acc[i][j][r] * p.alpha + bv[j][r];
-            if (p.act != ACT_NONE && p.act != ACT_GELU_BWD) t = apply_act(t, p.act, p.fast_act);
+            if (p.act != ACT_NONE && !act_is_gelu_bwd(p.act)) t = apply_act(t, p.act, p.fast_act);
             v[r] = t;
           }
           stage_put<BM, BN>(stA, stB, wm, wn, lane, i, j, v);
@@ -145,8 +145,9 @@ __device__ __forceinline__ void unpack8(const uint4& u, float (&v)[8]) {
 // trunk.py _conv3_folded): the GEMM value is rounded to bf16 in the stage -- as the unfolded path stores y3 -- and the
 // residual is added per 16-B row chunk in the flush, so both the residual loads and the output stores are full rows.
 // ACT_GELU_BWD: the residual is the pre-activation and the output dh * GELU'(pre), dh rounded to bf16 first (as
-// torch autocast's bf16 matmul output feeding gelu_backward)
-template <int BM, int BN, bool GELU_BWD>
+// torch autocast's bf16 matmul output feeding gelu_backward); GELU_BWD 1: the erf form, 2: the tanh form
+// (ACT_GELU_TANH_BWD), 0: the residual is an addend
+template <int BM, int BN, int GELU_BWD>
 __device__ __forceinline__ void epilogue_staged_res(f32x4 (&acc)[4][BN / 32], const GemmParams& p,
                                                     const float (&bv)[BN / 32][4], bf16_t* Cout, const bf16_t* Res,
                                                     bf16_t* stA, bf16_t* stB, int m0, int n0, int wm, int wn,
@@ -205,9 +206,12 @@ __device__ __forceinline__ void epilogue_staged_res(f32x4 (&acc)[4][BN / 32], co
       for (int e = 0; e < 8; ++e) r[e] = fmaf(r[e], rsc[e], rsh[e]);
     }
     uint32_t mb = 0;  // ReLU mask of the output (p.obits): bit e = out > 0, as vcg_bn_apply writes it
-    if constexpr (GELU_BWD) {  // BERT FFN2's input gradient: dh * GELU'(pre), dh rounded as stored
+    if constexpr (GELU_BWD == 1) {  // BERT FFN2's input gradient: dh * GELU'(pre), dh rounded as stored
 #pragma unroll
       for (int e = 0; e < 8; ++e) a[e] *= p.fast_act ? gelu_erf_grad_fast(r[e]) : gelu_erf_grad(r[e]);
+    } else if constexpr (GELU_BWD == 2) {  // GPT's: the tanh form
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] *= p.fast_act ? gelu_tanh_grad_fast(r[e]) : gelu_tanh_grad(r[e]);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -1389,10 +1393,10 @@ __device__ __forceinline__ void igemm_fast_body(const GemmParams& p) {
                                ((uintptr_t)p.C & 15) == 0)) {
         epilogue_staged<BM, BN>(acc, p, bv, Cout, stA, stB, mt * BM, n0, wm, wn, lane, p.M);
       } else if (RES && (staged || p.obits) && p.aux == nullptr &&
-                 (RES == 2 ? (staged && !p.res_sc) : (p.res_round && p.act == ACT_RELU)) &&
+                 (RES >= 2 ? (staged && !p.res_sc) : (p.res_round && p.act == ACT_RELU)) &&
                  ((p.ldc | p.ldr | p.N) & 7) == 0 && (((uintptr_t)p.residual | (uintptr_t)p.C) & 15) == 0) {
         if constexpr (BM == 128 && RES)
-          epilogue_staged_res<BM, BN, RES == 2>(acc, p, bv, Cout, Res, stA, stB, mt * BM, n0, wm, wn, lane, p.M);
+          epilogue_staged_res<BM, BN, RES >= 2 ? RES - 1 : 0>(acc, p, bv, Cout, Res, stA, stB, mt * BM, n0, wm, wn, lane, p.M);
       } else {
         if constexpr (BM == 128)
           gemm_epilogue<bf16_t, BM, BN, EPI>(acc, p, red, bv, Cout, Res, mt * BM, n0, wm, wn, lane, mt, mtiles);
@@ -2228,11 +2232,12 @@ int run_fast_gemm(GemmParams& p, int amode, int epi, int z, hipStream_t s) {
     if (amode == OP_DGRAD) return fast_bn<OP_DGRAD, EPI_STATS>(p, z, s);
     return fast_bn<OP_DENSE_K, EPI_STATS>(p, z, s);
   }
-  // dense layers only; RES = 2: the GELU' x residual epilogue (BERT FFN2's input gradient) as its own kernel -- in
+  // dense layers only; RES = 2 (erf) / 3 (tanh): the GELU' x residual epilogue (FFN2's input gradient) as its own kernel -- in
   // the ReLU / add instantiation its erf code raised register use and slowed the scoring forward's folded conv3
   // GEMMs by ~10 % (2.72-2.76 K vs 3.06 K windows/s, bisected to that change)
-  if (p.residual) return p.act == ACT_GELU_BWD ? fast_bn<OP_DENSE_K, EPI_STORE, 2>(p, z, s)
-                                               : fast_bn<OP_DENSE_K, EPI_STORE, 1>(p, z, s);
+  if (p.residual) return p.act == ACT_GELU_BWD        ? fast_bn<OP_DENSE_K, EPI_STORE, 2>(p, z, s)
+                         : p.act == ACT_GELU_TANH_BWD ? fast_bn<OP_DENSE_K, EPI_STORE, 3>(p, z, s)
+                                                      : fast_bn<OP_DENSE_K, EPI_STORE, 1>(p, z, s);
   if (p.aux && amode == OP_DENSE_K && (p.ldc & 7) == 0)  // a GELU input kept for the backward
     return fast_bn<OP_DENSE_K, EPI_STORE_AUX>(p, z, s);
   if (amode == OP_IM2COL_SMALLC) return fast_bn<OP_IM2COL_SMALLC, EPI_STORE>(p, z, s);

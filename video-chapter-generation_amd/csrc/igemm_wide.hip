@@ -33,7 +33,7 @@ __device__ __forceinline__ int w_xcd_slot(int b, int n) {
 
 }  // namespace
 
-enum { WE_STORE = 0, WE_GELU = 1, WE_GELU_BWD = 2, WE_RES = 3, WE_RES32 = 4 };
+enum { WE_STORE = 0, WE_GELU = 1, WE_GELU_BWD = 2, WE_RES = 3, WE_RES32 = 4, WE_GELU_TANH = 5, WE_GELU_TANH_BWD = 6 };
 
 namespace {
 
@@ -45,6 +45,7 @@ namespace {
 //                autocast's GELU of the rounded Linear output: the oracle-anchored step's BERT gradients measured
 //                1.24e-2 from fp64 with the rounded input, against autocast's 0.82e-2)
 //   WE_GELU_BWD  C = bf16(bf16(acc + bias) * gelu'(res)), res = the saved pre-activation
+//   WE_GELU_TANH, WE_GELU_TANH_BWD  the same two with the tanh form of GELU (ACT_GELU_TANH, ACT_GELU_TANH_BWD)
 //   WE_RES       C = bf16(acc + bias + res)
 //   WE_RES32     C = acc + bias + res with res and C fp32 (BERT's input gradients on its fp32 residual-gradient stream)
 __device__ const float4 g_wide_zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -54,7 +55,7 @@ __device__ __forceinline__ void wide_epilogue(f32x4 (&acc)[MT][NT], const GemmPa
   bf16_t* C = reinterpret_cast<bf16_t*>(p.C);
   const bf16_t* R = reinterpret_cast<const bf16_t*>(p.residual);
   float rv[MT][NT][4];
-  if constexpr (WE == WE_GELU_BWD || WE == WE_RES || WE == WE_RES32) {
+  if constexpr (WE == WE_GELU_BWD || WE == WE_GELU_TANH_BWD || WE == WE_RES || WE == WE_RES32) {
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -87,6 +88,12 @@ __device__ __forceinline__ void wide_epilogue(f32x4 (&acc)[MT][NT], const GemmPa
         } else if constexpr (WE == WE_GELU_BWD) {
           t = bf2f(f2bf(t));
           v[r] = t * (p.fast_act ? gelu_erf_grad_fast(rv[i][j][r]) : gelu_erf_grad(rv[i][j][r]));
+        } else if constexpr (WE == WE_GELU_TANH) {
+          v[r] = p.fast_act ? gelu_tanh_fast(t) : gelu_tanh(t);
+          acc[i][j][r] = t;
+        } else if constexpr (WE == WE_GELU_TANH_BWD) {
+          t = bf2f(f2bf(t));
+          v[r] = t * (p.fast_act ? gelu_tanh_grad_fast(rv[i][j][r]) : gelu_tanh_grad(rv[i][j][r]));
         } else if constexpr (WE == WE_RES || WE == WE_RES32) {
           v[r] = t + rv[i][j][r];
         } else {
@@ -98,7 +105,7 @@ __device__ __forceinline__ void wide_epilogue(f32x4 (&acc)[MT][NT], const GemmPa
           store4<float>(reinterpret_cast<float*>(p.C) + (long long)m * p.ldc + n, v);
         else
           store4<bf16_t>(C + (long long)m * p.ldc + n, v);
-        if constexpr (WE == WE_GELU) {
+        if constexpr (WE == WE_GELU || WE == WE_GELU_TANH) {
           if (p.aux) {
             const float a4[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
             store4<bf16_t>(reinterpret_cast<bf16_t*>(p.aux) + (long long)m * p.ldc + n, a4);
@@ -354,6 +361,8 @@ void launch_wide_we(const GemmParams& p, int we, hipStream_t s) {
     case WE_GELU_BWD: launch_wide<BN, WE_GELU_BWD>(p, s); break;
     case WE_RES: launch_wide<BN, WE_RES>(p, s); break;
     case WE_RES32: launch_wide<BN, WE_RES32>(p, s); break;
+    case WE_GELU_TANH: launch_wide<BN, WE_GELU_TANH>(p, s); break;
+    case WE_GELU_TANH_BWD: launch_wide<BN, WE_GELU_TANH_BWD>(p, s); break;
     default: launch_wide<BN, WE_STORE>(p, s); break;
   }
 }
@@ -369,13 +378,15 @@ int wide_gemm_class(const GemmParams& p) {
   if ((((uintptr_t)p.C | (uintptr_t)p.a.ptr | (uintptr_t)p.b.ptr) & 15) != 0) return -1;
   if (p.a.bytes >= 0xFFFFFF00LL || p.b.bytes >= 0xFFFFFF00LL) return -1;
   if (p.bias && ((uintptr_t)p.bias & 15) != 0) return -1;
-  if (p.aux && (p.act != ACT_GELU || ((uintptr_t)p.aux & 15) != 0)) return -1;
+  if (p.aux && ((p.act != ACT_GELU && p.act != ACT_GELU_TANH) || ((uintptr_t)p.aux & 15) != 0)) return -1;
   if (p.residual) {
     if (p.residual == p.C || (p.ldr & 3) != 0 || ((uintptr_t)p.residual & 7) != 0) return -1;
     if (p.act == ACT_GELU_BWD) return WE_GELU_BWD;
+    if (p.act == ACT_GELU_TANH_BWD) return WE_GELU_TANH_BWD;
     return p.act == ACT_NONE && !p.res_round ? WE_RES : -1;
   }
   if (p.act == ACT_GELU) return WE_GELU;
+  if (p.act == ACT_GELU_TANH) return WE_GELU_TANH;
   return p.act == ACT_NONE ? WE_STORE : -1;
 }
 

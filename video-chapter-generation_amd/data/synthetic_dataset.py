@@ -49,6 +49,30 @@ class HashTokenizer:
         return out
 
 
+class _Encoding:
+    """What a transformers tokenizer call returns, as far as the datasets read it: `.data["input_ids"]`."""
+
+    def __init__(self, ids):
+        self.data = {"input_ids": ids}
+
+
+class HashGPTTokenizer:
+    """A deterministic stand-in for transformers.OpenAIGPTTokenizer where its vocabulary files are absent: calling it
+    splits the text on whitespace (lower-cased) and gives every word an FNV-1a hash in [0, vocab_size)."""
+
+    def __init__(self, vocab_size=40478):
+        self.vocab_size = vocab_size
+
+    def __call__(self, text):
+        ids = []
+        for t in text.lower().split():
+            h = 0xCBF29CE484222325
+            for b in t.encode():
+                h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+            ids.append(h % self.vocab_size)
+        return _Encoding(ids)
+
+
 def normalize_frames(u8):
     """u8 [..., H, W, 3] -> f32 [..., 3, H, W] as ToTensor + Normalize (fp32)."""
     x = torch.from_numpy(np.ascontiguousarray(u8)).float() / 255.0

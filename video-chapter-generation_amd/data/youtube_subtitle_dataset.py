@@ -10,10 +10,17 @@ masked-LM pre-training sampler of pretrain_lang_model_hugface.py: same construct
 - the text is every subtitle starting inside (t - T/2 - 4, t + T/2 + 4), joined by spaces (:317-326);
 - `bert` branch (:349-402): "[CLS] " + text, tokenised, truncated to max_text_len, masked by `mask_tokens`, padded
   with "[PAD]" (attention mask 0), converted to ids; the targets are the original ids at the masked positions;
-- `gpt` (next-token targets, :329-347) is outside this port: the constructor raises.
+- `gpt` (next-token targets, :329-347) is not a branch of this class: the constructor raises. The generative stage
+  has a class of its own, `YoutubeClipSubtitleDatasetForGPT` (below), next to the contrastive stage's.
 
 `SyntheticSubtitleDatasetForHugFace` runs the same sampler over data/synthetic_dataset.py's corpus, so the driver runs
 with no data on disk.
+
+`YoutubeClipSubtitleDatasetForGPT(data_file, vid_file, tokenizer, clip_frame_num, max_text_len, subtitle_dir=None)` is
+the reference class's `gpt` branch (:329-347) over the same clip sampler: ids = tokenizer(text).data["input_ids"],
+x = ids[:-1], y = ids[1:], both truncated to max_text_len and padded with X_PAD / Y_PAD; the attention mask is 1 over
+len(y). item i -> (x i64 [L], y i64 [L] (-1 = padding), attention_mask i64 [L]). `SyntheticSubtitleDatasetForGPT` is
+its synthetic-corpus twin.
 
 `YoutubeClipConstrastSubtitleDataset` (:415-551) is the shot-contrastive sampler of
 train_lang/pretrain_constrast_lang_model.py:
@@ -128,6 +135,59 @@ class YoutubeClipSubtitleDatasetForHugFace(torch.utils.data.Dataset):
         h = self.half_clip_frame_num
         t = random.sample(list(range(h, image_num - h)), k=1)[0]
         return encode_mlm(self.tokenizer, clip_text(subtitles, t, h), self.max_text_len, random)
+
+
+def encode_gpt(tokenizer, text, max_text_len, vocab_size=None):
+    """:329-347 -> (x, y, attention_mask) as int64 tensors of max_text_len: next-token pairs of the tokenised text.
+    vocab_size: an id outside [0, vocab_size) is a ValueError here, on the host (the model's embedding kernels index
+    the table by id and do not check)."""
+    ids = list(tokenizer(text).data["input_ids"])
+    if vocab_size is not None and ids and not (0 <= min(ids) and max(ids) < vocab_size):
+        raise ValueError(f"encode_gpt: token id outside [0, {vocab_size}) (a tokenizer with another vocabulary?)")
+    x = ids[:-1][:max_text_len]
+    y = ids[1:][:max_text_len]
+    mask = [1] * len(y)
+    n_pad = max(0, max_text_len - len(x))
+    x = x + [X_PAD] * n_pad
+    y = y + [Y_PAD] * n_pad
+    mask = mask + [X_PAD] * n_pad
+    return tuple(torch.from_numpy(np.array(a, dtype=np.int64)).long() for a in (x, y, mask))
+
+
+class YoutubeClipSubtitleDatasetForGPT(YoutubeClipSubtitleDatasetForHugFace):
+    """The reference class with model_type "gpt" (:329-347): the masked-LM class's clip sampler, next-token targets."""
+
+    def __init__(self, data_file, vid_file, tokenizer, clip_frame_num, max_text_len, subtitle_dir=None,
+                 vocab_size=None):
+        super().__init__(data_file, vid_file, "bert", tokenizer, clip_frame_num, max_text_len, subtitle_dir)
+        self.model_type = "gpt"
+        self.vocab_size = vocab_size  # (optional: ids are checked against it, see encode_gpt)
+
+    def __getitem__(self, i):
+        vid = self.vids[i]
+        image_num = round(self.vid2durations[vid] - 1)
+        with open(self.vid2asr_files[vid]) as f:
+            subtitles = json.load(f)
+        h = self.half_clip_frame_num
+        t = random.sample(list(range(h, image_num - h)), k=1)[0]
+        return encode_gpt(self.tokenizer, clip_text(subtitles, t, h), self.max_text_len, self.vocab_size)
+
+
+class SyntheticSubtitleDatasetForGPT(torch.utils.data.Dataset):
+    """The same sampler over a data.synthetic_dataset.SyntheticVideoCorpus (image_num frames at 1 fps)."""
+
+    def __init__(self, corpus, tokenizer, clip_frame_num, max_text_len, vocab_size=None):
+        self.c, self.tokenizer, self.max_text_len, self.vocab_size = corpus, tokenizer, max_text_len, vocab_size
+        self.half_clip_frame_num = int(clip_frame_num // 2)
+
+    def __len__(self):
+        return len(self.c.vids)
+
+    def __getitem__(self, i):
+        vid = self.c.vids[i]
+        h = self.half_clip_frame_num
+        t = random.sample(list(range(h, self.c.image_num[vid] - h)), k=1)[0]
+        return encode_gpt(self.tokenizer, clip_text(self.c.subtitles[vid], t, h), self.max_text_len, self.vocab_size)
 
 
 def contrast_clips(t, clip_frame_num, neighbor_size):

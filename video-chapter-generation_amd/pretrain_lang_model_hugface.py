@@ -112,6 +112,10 @@ class Trainer:
                 self.save_checkpoint(epoch, best_loss)
         return best_loss
 
+    def step_loss(self, x, attention_mask, y):
+        """(loss, n_correct, n_valid) of one batch (the generative stage's trainer states its own)."""
+        return self.model.mlm_loss(x, attention_mask, y)
+
     def run_epoch(self, split, epoch):
         is_train = split == "train"
         self.model.train(is_train)
@@ -125,7 +129,7 @@ class Trainer:
             x = x.to(self.device)
             attention_mask = attention_mask.to(self.device)
             with torch.set_grad_enabled(is_train):
-                loss, n_correct, n_valid = self.model.mlm_loss(x, attention_mask, y)
+                loss, n_correct, n_valid = self.step_loss(x, attention_mask, y)
             if is_train and n_valid:
                 self.model.zero_grad()
                 loss.backward()

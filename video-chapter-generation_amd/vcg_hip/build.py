@@ -30,6 +30,29 @@ def build_mlm_model(seed=None, device=None, precision="bf16", dropout=None):
     return model
 
 
+def build_gpt_model(seed=None, device=None, precision="bf16", dropout=None, config=None, checkpoint=None):
+    """The generative pre-training driver's model (pretrain_lang_model_hugface.py:234, model_type "gpt"): GPTHugface()
+    with its vocabulary head. With a seed every parameter is seeded by name; checkpoint (or $VCG_GPT_CHECKPOINT): a
+    local HF openai-gpt state dict for the decoder, loaded AFTER the seeding."""
+    import os
+    from model.lang.gpt_hugface import GPTHugface
+    from vcg_hip.nn import OpenAIGPTConfig
+    cfg = config if config is not None else OpenAIGPTConfig()
+    if dropout is not None:
+        cfg.resid_pdrop = cfg.embd_pdrop = cfg.attn_pdrop = dropout
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = GPTHugface(config=cfg, checkpoint=checkpoint)
+    if device is not None:
+        model = model.to(device)
+    if seed is not None:
+        synth.init_params(model, seed)
+        ckpt = checkpoint or os.environ.get("VCG_GPT_CHECKPOINT")
+        if ckpt:  # (the seeding covered every parameter: the constructor's load is applied again)
+            model.load_checkpoint(ckpt)
+    model.precision = precision
+    return model
+
+
 def load_lang_pretrain(bert, path):
     """The hand-off of train_video_segment_point.py:326-330: the language model starts from the masked-LM stage's
     checkpoint (pretrain_lang_model_hugface.py's checkpoint["model_state_dict"], a BertHugface state dict with its

@@ -348,9 +348,141 @@ class BertModel(NativeRoot, nn.Module):
         return BertOutput(last.view(B, L, -1), pooled)
 
 
+# ============================================================================ OpenAI GPT
+class OpenAIGPTConfig:
+    """The subset of transformers.OpenAIGPTConfig the decoder uses (openai-gpt defaults). afn "gelu" is transformers'
+    NewGELUActivation (the tanh form), as ACT_FNS resolves it there."""
+
+    def __init__(self, vocab_size=40478, n_positions=512, n_embd=768, n_layer=12, n_head=12, afn="gelu",
+                 resid_pdrop=0.1, embd_pdrop=0.1, attn_pdrop=0.1, layer_norm_epsilon=1e-5, initializer_range=0.02,
+                 **kwargs):
+        self.vocab_size = vocab_size
+        self.n_positions = n_positions
+        self.n_embd = n_embd
+        self.n_layer = n_layer
+        self.n_head = n_head
+        self.afn = afn
+        self.resid_pdrop = resid_pdrop
+        self.embd_pdrop = embd_pdrop
+        self.attn_pdrop = attn_pdrop
+        self.layer_norm_epsilon = layer_norm_epsilon
+        self.initializer_range = initializer_range
+        for k, v in kwargs.items():
+            setattr(self, k, v)
+
+    hidden_size = property(lambda self: self.n_embd)
+    max_position_embeddings = property(lambda self: self.n_positions)
+
+
+class Conv1D(nn.Module):
+    """transformers.pytorch_utils.Conv1D: a Linear whose weight is stored [in, out] (y = x W + b)."""
+
+    def __init__(self, nf, nx):
+        super().__init__()
+        self.nf, self.nx = nf, nx
+        self.weight = nn.Parameter(torch.empty(nx, nf))
+        self.bias = nn.Parameter(torch.zeros(nf))
+
+
+class _GptAttention(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.c_attn = Conv1D(3 * c.n_embd, c.n_embd)
+        self.c_proj = Conv1D(c.n_embd, c.n_embd)
+        self.attn_dropout = nn.Dropout(c.attn_pdrop)
+        self.resid_dropout = nn.Dropout(c.resid_pdrop)
+
+
+class _GptMLP(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.c_fc = Conv1D(4 * c.n_embd, c.n_embd)
+        self.c_proj = Conv1D(c.n_embd, 4 * c.n_embd)
+        self.dropout = nn.Dropout(c.resid_pdrop)
+
+
+class _GptBlock(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.attn = _GptAttention(c)
+        self.ln_1 = nn.LayerNorm(c.n_embd, eps=c.layer_norm_epsilon)
+        self.mlp = _GptMLP(c)
+        self.ln_2 = nn.LayerNorm(c.n_embd, eps=c.layer_norm_epsilon)
+
+
+class GPTOutput:
+    """Subset of transformers' BaseModelOutput."""
+
+    def __init__(self, last_hidden_state):
+        self.last_hidden_state = last_hidden_state
+        self.hidden_states = self.attentions = None
+
+    def __getitem__(self, i):
+        return (self.last_hidden_state,)[i]
+
+
+class OpenAIGPTModel(NativeRoot, nn.Module):
+    """transformers.OpenAIGPTModel (the reference's model/lang/gpt_hugface.py:18) with its parameter names and shapes
+    -- `tokens_embed`, `positions_embed`, `h.{i}.attn.c_attn|c_proj`, `ln_1`, `mlp.c_fc|c_proj`, `ln_2`, Conv1D weights
+    [in, out] -- so state dicts are interchangeable; executed by vcg_hip/gpt.py's GptEncoderEngine (causal fused
+    attention, tanh-GELU epilogues).
+
+    Attention: key j is visible to query i iff j <= i and attention_mask[j] != 0. A query without any visible key is
+    uniform over all L keys, which is what transformers computes for a fully masked sequence (its -1e4 causal fill and
+    finfo.min padding fill are both absorbed). For a LEFT-padded mask (position 0 masked, a later one not) transformers
+    attends to the future valid keys instead, since its causal fill is finite; this model does not. The datasets here
+    only pad on the right."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = config if config is not None else OpenAIGPTConfig()
+        c = self.config
+        if c.afn not in ("gelu", "gelu_new"):
+            raise NotImplementedError(f"native OpenAIGPTModel implements afn='gelu' (the tanh form), not {c.afn!r}")
+        self.tokens_embed = nn.Embedding(c.vocab_size, c.n_embd)
+        self.positions_embed = nn.Embedding(c.n_positions, c.n_embd)
+        self.drop = nn.Dropout(c.embd_pdrop)
+        self.h = nn.ModuleList([_GptBlock(c) for _ in range(c.n_layer)])
+        std = c.initializer_range
+        for m in self.modules():
+            if isinstance(m, (Conv1D, nn.Embedding)):
+                nn.init.normal_(m.weight, 0.0, std)
+            elif isinstance(m, nn.LayerNorm):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+
+    def check_text_len(self, L):
+        P = self.config.n_positions
+        if L > P:
+            raise ValueError(f"OpenAIGPTModel: text length {L} exceeds n_positions {P}")
+
+    def native_forward(self, input_ids, attention_mask, hooks=None):
+        """Returns the last hidden state [B L, H] in the compute dtype (autograd-connected)."""
+        self.check_text_len(input_ids.shape[-1])
+        from .functions import BertFn
+        from .gpt import GptEncoderEngine
+        f = self.native_flat()
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        eng = GptEncoderEngine(self, f, self.compute_dtype())
+        _, last = BertFn.apply(input_ids, attention_mask, self._anchor(input_ids.device), eng,
+                               torch.is_grad_enabled(), new_seed(), hooks)
+        return last
+
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, **kwargs):
+        if token_type_ids is not None or position_ids is not None:
+            raise NotImplementedError("native OpenAIGPTModel takes input_ids and attention_mask (the reference passes "
+                                      "nothing else)")
+        B, L = input_ids.shape
+        return GPTOutput(self.native_forward(input_ids, attention_mask).view(B, L, -1))
+
+
 def check_max_text_len(model, max_text_len):
     """Drivers: --max_text_len against the position table of every BertModel inside `model`, before any data is built."""
     for m in model.modules():
         if isinstance(m, BertModel) and max_text_len > m.config.max_position_embeddings:
             raise SystemExit(f"error: --max_text_len {max_text_len} exceeds the language model's "
                              f"{m.config.max_position_embeddings} positions (BertConfig.max_position_embeddings)")
+        if isinstance(m, OpenAIGPTModel) and max_text_len > m.config.n_positions:
+            raise SystemExit(f"error: --max_text_len {max_text_len} exceeds the language model's "
+                             f"{m.config.n_positions} positions (OpenAIGPTConfig.n_positions)")

@@ -12,6 +12,8 @@ from . import _lib
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH, ACT_GELU_BWD = 0, 1, 2, 3, 4
+ACT_GELU_TANH, ACT_GELU_TANH_BWD = 5, 6  # the tanh form of GELU (OpenAIGPT's afn) and its derivative of a residual
+ATTN_CAUSAL = 1  # vcg_bert_attn_*_ex / vcg_attn_softmax_fwd_ex flag (vcg_hip.h VCG_ATTN_CAUSAL)
 ACT_FLAG_ROUND_PRE = 0x100  # gemm: round alpha*AB + bias to the storage dtype before the residual (vcg_hip.h)
 ACT_FLAG_WIDE = 0x200  # gemm: the wide-tile engine (BERT's Linear layers, the downsample dgrad; vcg_hip.h VCG_ACT_FLAG_WIDE)
 ACT_FLAG_F32_OUT = 0x400  # gemm (wide, bf16 operands): fp32 residual and output (vcg_hip.h VCG_ACT_FLAG_F32_OUT)
@@ -747,12 +749,42 @@ def colsum(x, ld, rows, N, out, accumulate=True):
               stream())
 
 
-def attn_softmax_fwd(S, mask, P_out, Pd_out, B, nh, L, Lp, scale, p=0.0, seed=0):
+def gpt_embed_fwd(ids, tok, pos, B, L, H, dtype, p=0.0, seed=0):
+    """OpenAIGPT's embedding: dropout(tok[ids] + pos[t]) -> [B*L, H] (no token types, no LayerNorm)."""
+    out = torch.empty((B * L, H), dtype=dtype, device=ids.device)
+    _lib.call("vcg_gpt_embed_fwd", dt_code(dtype), P(ids), P(tok), P(pos), P(out), B, L, H, float(p),
+              int(seed) & (2**64 - 1), stream())
+    return out
+
+
+def gpt_embed_bwd(dout, ids, tok_grad, pos_grad, B, L, H, p=0.0, seed=0, storage_dtype=None):
+    """Backward of gpt_embed_fwd: fp32 token / position gradients ADDED onto tok_grad / pos_grad (either may be None),
+    fixed order, no atomics. dout: the forward's dtype, or fp32 (the residual-gradient stream of a bf16 forward)."""
+    nbytes = _lib.query("vcg_ln_bwd_ws_bytes", B * L, H)
+    w = ws(nbytes, dout.device)
+    code = dt_code(dout.dtype)
+    if storage_dtype is not None and storage_dtype != dout.dtype:
+        if not (storage_dtype == torch.bfloat16 and dout.dtype == torch.float32):
+            raise TypeError(f"gpt_embed_bwd: dout {dout.dtype} with a {storage_dtype} forward")
+        code = BF16 | GRAD_F32
+    _lib.call("vcg_gpt_embed_bwd", code, P(dout), P(ids), P(tok_grad), P(pos_grad), P(w), w.numel() * 4, B, L, H,
+              float(p), int(seed) & (2**64 - 1), stream())
+
+
+def attn_softmax_fwd(S, mask, P_out, Pd_out, B, nh, L, Lp, scale, p=0.0, seed=0, causal=False):
+    if causal:
+        _lib.call("vcg_attn_softmax_fwd_ex", dt_code(S.dtype), P(S), P(mask), P(P_out), P(Pd_out), B, nh, L, Lp,
+                  float(scale), float(p), int(seed) & (2**64 - 1), ATTN_CAUSAL, stream())
+        return
     _lib.call("vcg_attn_softmax_fwd", dt_code(S.dtype), P(S), P(mask), P(P_out), P(Pd_out), B, nh, L, Lp,
               float(scale), float(p), int(seed) & (2**64 - 1), stream())
 
 
-def attn_softmax_bwd(dPd, Pm, dS, Z, L, Lp, scale, p=0.0, seed=0):
+def attn_softmax_bwd(dPd, Pm, dS, Z, L, Lp, scale, p=0.0, seed=0, causal=False):
+    if causal:
+        _lib.call("vcg_attn_softmax_bwd_ex", dt_code(dPd.dtype), P(dPd), P(Pm), P(dS), Z, L, Lp, float(scale),
+                  float(p), int(seed) & (2**64 - 1), ATTN_CAUSAL, stream())
+        return
     _lib.call("vcg_attn_softmax_bwd", dt_code(dPd.dtype), P(dPd), P(Pm), P(dS), Z, L, Lp, float(scale), float(p),
               int(seed) & (2**64 - 1), stream())
 
@@ -763,12 +795,16 @@ def bert_attn_stats(B, nh, L, device):
     return torch.empty(_lib.query("vcg_bert_attn_stats_bytes", B, nh, L) // 4, dtype=torch.float32, device=device)
 
 
-def bert_attn_fwd(qkv, mask, ctx, stats, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None):
+def bert_attn_fwd(qkv, mask, ctx, stats, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None, causal=False):
     """Fused attention forward (bf16, L <= 512, head dim 64; L > 128: the tiled online-softmax kernels): qkv
     [B*L(+pad), 3H] -> ctx [B*L, H]; stats: bert_attn_stats(B, nh, L).
     seq (int32 [B+1]): packed sequences, rows seq[b] .. seq[b+1]-1 (L = the longest, mask = the packed rows' key
-    flags; vcg_bert_attn_fwd_varlen)."""
-    if seq is None:
+    flags; vcg_bert_attn_fwd_varlen). causal: key j is visible to query i iff j <= i and mask[j] != 0; tiles above the
+    diagonal are skipped (vcg_bert_attn_fwd_ex)."""
+    if causal:
+        _lib.call("vcg_bert_attn_fwd_ex", P(qkv), P(mask), P(seq), P(ctx), P(stats), B, nh, L, Lp, float(scale),
+                  float(p), int(seed) & (2**64 - 1), ATTN_CAUSAL, stream())
+    elif seq is None:
         _lib.call("vcg_bert_attn_fwd", P(qkv), P(mask), P(ctx), P(stats), B, nh, L, Lp, float(scale), float(p),
                   int(seed) & (2**64 - 1), stream())
     else:
@@ -776,10 +812,13 @@ def bert_attn_fwd(qkv, mask, ctx, stats, B, nh, L, Lp, scale, p=0.0, seed=0, seq
                   float(p), int(seed) & (2**64 - 1), stream())
 
 
-def bert_attn_bwd(qkv, dctx, ctx, mask, stats, dqkv, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None):
+def bert_attn_bwd(qkv, dctx, ctx, mask, stats, dqkv, B, nh, L, Lp, scale, p=0.0, seed=0, seq=None, causal=False):
     """Backward of bert_attn_fwd: dqkv [B*L, 3H] = dQ | dK | dV (deterministic; ctx may be None). At L > 128 it writes
-    its D vector into the tail of `stats`."""
-    if seq is None:
+    its D vector into the tail of `stats`. causal: as the forward's."""
+    if causal:
+        _lib.call("vcg_bert_attn_bwd_ex", P(qkv), P(dctx), P(mask), P(seq), P(stats), P(dqkv), B, nh, L, Lp,
+                  float(scale), float(p), int(seed) & (2**64 - 1), ATTN_CAUSAL, stream())
+    elif seq is None:
         _lib.call("vcg_bert_attn_bwd", P(qkv), P(dctx), P(ctx), P(mask), P(stats), P(dqkv), B, nh, L, Lp, float(scale),
                   float(p), int(seed) & (2**64 - 1), stream())
     else:

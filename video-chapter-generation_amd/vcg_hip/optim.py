@@ -18,14 +18,15 @@ def _no_decay(full_name, leaf_name):
     return leaf_name.endswith("bias") or any(tag in full_name for tag in ("LayerNorm", "bn", "emb"))
 
 
-def param_groups(model, weight_decay):
-    """[decay group, no-decay group] over every parameter, each sorted by name (the reference's order)."""
+def param_groups(model, weight_decay, no_decay=_no_decay):
+    """[decay group, no-decay group] over every parameter, each sorted by name (the reference's order). no_decay(full
+    name, leaf name): the grouping rule (default: TwoStream's)."""
     named = dict(model.named_parameters())
     owner = {}  # full name -> decided by the module that owns it directly
     for mod_name, mod in model.named_modules():
         for leaf, _ in mod.named_parameters(recurse=False):
             full = f"{mod_name}.{leaf}" if mod_name else leaf
-            owner[full] = _no_decay(full, leaf)
+            owner[full] = no_decay(full, leaf)
     unassigned = set(named) - set(owner)
     if unassigned:
         raise ValueError(f"param_groups: no owning module found for {sorted(unassigned)}")
@@ -37,9 +38,9 @@ def param_groups(model, weight_decay):
     ]
 
 
-def configure_adamw(model, train_config, skip=()):
+def configure_adamw(model, train_config, skip=(), no_decay=_no_decay):
     """skip: parameters the step leaves bit-unchanged, like those with requires_grad False (no update, no decay)."""
-    groups = param_groups(model, train_config.weight_decay)
+    groups = param_groups(model, train_config.weight_decay, no_decay)
     return FusedAdamW(groups, lr=train_config.learning_rate, betas=train_config.betas, model=model, skip=skip)
 
 

@@ -107,7 +107,7 @@ def init_rule(name, shape):
             small = ".bn3." in "." + name or "downsample.1" in name
             return (KIND_UNIFORM, 0.2, 0.6) if small else (KIND_UNIFORM, 0.5, 1.5)
         return KIND_UNIFORM, -0.2, 0.2
-    if "LayerNorm" in name:
+    if "LayerNorm" in name or ".ln_1." in name or ".ln_2." in name:  # (ln_1 / ln_2: OpenAIGPTModel's LayerNorms)
         return (KIND_UNIFORM, 0.8, 1.2) if leaf == "weight" else (KIND_UNIFORM, -0.1, 0.1)
     if "fusion_head" in name or name.startswith(("head.", "lang_proj_head", "vision_proj_head")):
         if len(shape) == 1 and leaf == "weight":  # LayerNorm gamma of the window ChapterHead's projection chains

@@ -1,4 +1,4 @@
-"""The LDS-patch 3x3 convolution (igemm_fast.hip conv3x3_patch_kernel: 3x3 / stride 1 / pad 1 over C = 64, the
+"""The LDS-patch 3x3 convolution (conv_patch.hip conv3x3_patch_kernel: 3x3 / stride 1 / pad 1 over C = 64, the
 layer-1 conv2 of the trunk) against float64 torch and against the im2col engine it replaces.
 
 Both engines accumulate the same bf16 products tap by tap with the same MFMA instruction and operand layout,

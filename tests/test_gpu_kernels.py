@@ -540,6 +540,10 @@ DGRAD_BWD_CASES = [
     (8, 6, 6, 128, 64, 1, 1, 0, 8),    # wider C: BN = 128 tiles
     (8, 7, 9, 256, 128, 1, 1, 0, 4),   # 1x1, K = 128 (streaming kernel, 3-deep ring), M = 504: a ragged last tile
     (4, 14, 14, 512, 64, 1, 1, 0, 4),  # 1x1, K = 64, 8 column tiles (streaming kernel, 4-deep ring), fold 64
+    # 1x1, K = 256, M = 100 (two tiles, the last ragged; odd H, W for the compact stride-2 residual): without mask
+    # bits (tsm_plain / tsm_strided_res) the streaming kernels' XF = 0 forms, 128 columns (fold 128) / 64 (fold 64)
+    (4, 5, 5, 1024, 256, 1, 1, 0, 4),
+    (4, 5, 5, 512, 256, 1, 1, 0, 4),
 ]
 
 
@@ -616,7 +620,10 @@ def test_conv_dgrad_bwd(K, case, mode):
 # the trunk's conv1 input gradients that the streaming EPI_BWD kernel takes (layers 1-3 at 16 frames; K = 256: layer 3,
 # one A tile per ring slot and the weights in registers): (N, H, W, C, Cout, T, res_stride)
 STREAM_CASES = [(16, 56, 56, 256, 64, 8, 1), (16, 28, 28, 512, 128, 8, 1), (16, 56, 56, 256, 128, 8, 2),
-                (16, 14, 14, 1024, 256, 8, 1), (16, 28, 28, 512, 256, 8, 2), (5, 14, 14, 1024, 256, 5, 1)]
+                (16, 14, 14, 1024, 256, 8, 1), (16, 28, 28, 512, 256, 8, 2), (5, 14, 14, 1024, 256, 5, 1),
+                # M = 8624: 135 M-tiles (the last of 48 rows) on 32 tile rows, 4-5 tiles per workgroup of the 128-column
+                # K = 256 kernel (3 ring slots): its steady-state counted vmcnt wait runs; 8-9 tiles at 64 columns
+                (44, 14, 14, 1024, 256, 4, 1)]
 
 
 @pytest.mark.parametrize("case", STREAM_CASES)
@@ -655,6 +662,43 @@ def test_conv_dgrad_bwd_stream_vs_persistent(K, case, ops_, monkeypatch):
         assert torch.equal(ga, gb), f"g differs: max {(ga.float() - gb.float()).abs().max().item():.3e}"
         for a, b in ((sa, sb), (xa, xb)):
             assert (a.double() - b.double()).abs().max().item() <= 1e-4 * (b.abs().max().item() + 1.0)
+
+
+# (case of STREAM_CASES' layout, VCG_BWD_STREAM, mask bits, census tag of the launch meant)
+STREAM_ROUTES = [
+    ((44, 14, 14, 1024, 256, 4, 1), "1", True, "igemm_fast_stream tn128 xf4"),
+    ((44, 14, 14, 1024, 256, 4, 1), "64", True, "igemm_fast_stream tn64 xf4"),
+    ((4, 5, 5, 1024, 256, 4, 1), "1", False, "igemm_fast_stream tn128 xf0"),
+    ((4, 5, 5, 1024, 256, 4, 2), "64", False, "igemm_fast_stream tn64 xf0"),
+    ((4, 5, 5, 512, 256, 4, 1), "1", False, "igemm_fast_stream tn64 xf0"),
+    ((4, 5, 5, 512, 256, 4, 2), "1", False, "igemm_fast_stream tn64 xf0"),
+]
+
+
+@pytest.mark.parametrize("case,flag,with_bits,tag", STREAM_ROUTES)
+def test_conv_dgrad_bwd_stream_routing(K, case, flag, with_bits, tag, monkeypatch):
+    """The K = 256 cases of test_conv_dgrad_bwd_stream_vs_persistent and test_conv_dgrad_bwd launch the streaming
+    kernel meant (the GEMM census names it), not the persistent engine, which would pass those tests as well."""
+    N, H, W, C, Cout, T, rs = case
+    dtype = torch.bfloat16
+    dy = _rand((N, H, W, Cout), dtype, 71).to(DEV)
+    wt = K.weight_prep(_rand((Cout, C, 1, 1), torch.float32, 72, 0.1).to(DEV), C, dtype, transposed=True)
+    res = _rand((N, (H + 1) // 2, (W + 1) // 2, C) if rs == 2 else (N, H, W, C), dtype, 75).to(DEV)
+    kw = {}
+    if with_bits:
+        _, bits = K.bn_apply(_rand((N, H, W, C), dtype, 76).to(DEV), torch.ones(C, device=DEV),
+                             torch.zeros(C, device=DEV), C, relu=True, bits=True)
+        kw = dict(bits=bits, mean=torch.zeros(C, device=DEV), invstd=torch.ones(C, device=DEV),
+                  sums=torch.zeros((2, C), device=DEV))
+    monkeypatch.setenv("VCG_BWD_STREAM", flag)
+    K.gemm_census_enable(True)
+    g = K.conv_dgrad_bwd(dy, wt, N, H, W, C, Cout, 1, 1, 1, 0, tsm_T=T, tsm_fold=C // 8, res=res, res_stride=rs, **kw)
+    torch.cuda.synchronize()
+    keys = list(K.gemm_census())
+    K.gemm_census_enable(False)
+    assert g is not None
+    assert f"{tag} M={N * H * W} N={C} K={Cout}" in keys, keys
+    assert not [k for k in keys if k.startswith("igemm_fast ")], keys
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

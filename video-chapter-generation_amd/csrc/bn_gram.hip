@@ -31,17 +31,15 @@
 // gram_finish writes the uncentred f32 G = Gc + d c^T + c d^T + M c c^T and colsum = d + M c; the statistics read
 // g64 (Cov = Gc / M - (d / M)(d / M)^T, mu = c + d / M: no cancellation against the centre).
 #include "bn_steps.h"
+#include "mfma_util.h"
 
 namespace vcg {
 namespace {
 
-typedef __attribute__((address_space(3))) char lds_char_t;
-__device__ __forceinline__ uint32_t lds_off(const void* p) { return (uint32_t)(uintptr_t)(const lds_char_t*)p; }
-
 // 16-B slot of logical chunk c in k-row `row` of a [64][COLS] bf16 panel (an involution in c; igemm_wgrad.hip wswz)
 template <int COLS> __device__ __forceinline__ int gswz(int row, int c) {
   if constexpr (COLS == 128) return c ^ (2 * (row & 7));
-  else return c ^ (2 * ((row >> 1) & 3));
+  else return tr_swz64(row, c);
 }
 
 // 16x16x32 fragment of columns r0..r0+15 of a [64][COLS] panel, k-substep s2 (rows 32 s2 .. + 31): element j of
@@ -52,22 +50,13 @@ __device__ __forceinline__ s16x8 gfrag(const bf16_t* panel, int r0, int lane, in
   const int q = i >> 2, pp = i & 3;
   const int cl = r0 + 4 * pp;
   const int k0 = 32 * s2 + 4 * g + q, k1 = k0 + 16;
-  const uint32_t a0 = lds_off(panel + k0 * COLS + 8 * gswz<COLS>(k0, cl >> 3) + (cl & 7));
-  const uint32_t a1 = lds_off(panel + k1 * COLS + 8 * gswz<COLS>(k1, cl >> 3) + (cl & 7));
+  const uint32_t a0 = lds_u32(panel + k0 * COLS + 8 * gswz<COLS>(k0, cl >> 3) + (cl & 7));
+  const uint32_t a1 = lds_u32(panel + k1 * COLS + 8 * gswz<COLS>(k1, cl >> 3) + (cl & 7));
   s16x4 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a0) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(a1) : "memory");
+  lds_tr_b16(lo, a0);
+  lds_tr_b16(hi, a1);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-__device__ __forceinline__ void unpack8g(const uint4& u, float (&v)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
 }
 
 // Gram block pair p (jb <= kb of 16 x 16, row-major over the upper triangle) -> jb, kb
@@ -157,27 +146,27 @@ __device__ __forceinline__ void gram_body(const bf16_t* __restrict__ y, const fl
       const int lr = r0 + u * RS;  // row within the iteration
       const long long row = it * R + lr;
       float a[8];
-      unpack8g(v[u], a);
+      unpack8(v[u], a);
       uint4 o = make_uint4(0u, 0u, 0u, 0u), d = make_uint4(0u, 0u, 0u, 0u);
       if (row < P) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] = fmaxf(fmaf(a[e], sc[e], sh[e]), 0.f);
-        o.x = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[1]) << 16);
-        o.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
-        o.z = (uint32_t)f2bf(a[4]) | ((uint32_t)f2bf(a[5]) << 16);
-        o.w = (uint32_t)f2bf(a[6]) | ((uint32_t)f2bf(a[7]) << 16);
+        o.x = pack2bf(a[0], a[1]);
+        o.y = pack2bf(a[2], a[3]);
+        o.z = pack2bf(a[4], a[5]);
+        o.w = pack2bf(a[6], a[7]);
         *reinterpret_cast<uint4*>(out + row * C + 8 * cc) = o;
         float st[8];
-        unpack8g(o, st);  // the stored (rounded) values
+        unpack8(o, st);  // the stored (rounded) values
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           st[e] -= ctr[e];  // (exact in f32; exact in bf16 for a 0 centre and, by Sterbenz, for c / 2 <= a <= 2 c)
           cs[0][e] += st[e];
         }
-        d.x = (uint32_t)f2bf(st[0]) | ((uint32_t)f2bf(st[1]) << 16);
-        d.y = (uint32_t)f2bf(st[2]) | ((uint32_t)f2bf(st[3]) << 16);
-        d.z = (uint32_t)f2bf(st[4]) | ((uint32_t)f2bf(st[5]) << 16);
-        d.w = (uint32_t)f2bf(st[6]) | ((uint32_t)f2bf(st[7]) << 16);
+        d.x = pack2bf(st[0], st[1]);
+        d.y = pack2bf(st[2], st[3]);
+        d.z = pack2bf(st[4], st[5]);
+        d.w = pack2bf(st[6], st[7]);
       }
       // LDS: k-step lr / 64, k-row lr % 64, panel cc / (COLS / 8), swizzled slot of chunk cc % (COLS / 8)
       const int ks = lr >> 6, kr = lr & 63, pn = cc / (COLS / 8), pc = cc % (COLS / 8);

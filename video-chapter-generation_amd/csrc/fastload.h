@@ -1,13 +1,13 @@
-// LDS-DMA operand loader of the bf16 fast GEMM engines (igemm_fast.hip, igemm256.hip): K-contiguous A / B tiles of
-// [rows][64] bf16 go global -> LDS with buffer_load ... lds (16 B per lane, 1 KiB per wave instruction), 16-B chunk c of
-// row r at slot c ^ ((r >> 1) & 7) (the global source address is pre-swizzled: LDS-DMA writes lane-linear), with the
-// conv gathers (im2col + TSM shift, dgrad, sub-pixel stride-2 classes) computed per row once per tile.
+// LDS-DMA operand loader of the bf16 fast GEMM engines (igemm_fast.hip, conv_patch.hip, igemm256.hip,
+// igemm_wide.hip): K-contiguous A / B tiles of [rows][64] bf16 go global -> LDS with buffer_load ... lds (16 B per
+// lane, 1 KiB per wave instruction), 16-B chunk c of row r at slot c ^ ((r >> 1) & 7) (the global source address is
+// pre-swizzled: LDS-DMA writes lane-linear), with the conv gathers (im2col + TSM shift, dgrad, sub-pixel stride-2
+// classes) computed per row once per tile.
 #pragma once
 #include "igemm.h"
+#include "mfma_util.h"
 
 namespace vcg {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int FBK = 64;
 
@@ -235,9 +235,29 @@ __device__ __forceinline__ s16x8 fast_frag(const bf16_t* lds, int r0, int lane, 
   return *reinterpret_cast<const s16x8*>(lds + row * 64 + 8 * fswz(row, 4 * s2 + g));
 }
 
-__device__ __forceinline__ constexpr int waitcnt_vm(int n) {
-  // s_waitcnt simm16 for gfx9-family: vmcnt[3:0] | expcnt 7 << 4 | lgkmcnt 15 << 8 | vmcnt[5:4] << 14
-  return (n & 0xF) | (0x7 << 4) | (0xF << 8) | (((n >> 4) & 3) << 14);
+// EPI_BWD with none of the residual / mask-bit / y2 / TSM operands: the light (affine) epilogue, EPI_BWD_AFF
+static inline bool bwd_light(const GemmParams& p) {
+  const BwdEpi& e = p.bwd;
+  return !e.res && !e.bits && !e.y2 && e.tsm_T == 0;
+}
+
+// Algorithmic HBM bytes of one launch (bench.py's per-launch roofline): every operand read once (a gathered A:
+// the source tensor once), the output written once, the epilogue's extra operands read once (bf16).
+template <int AM, int EPI, int RES>
+static inline double algorithmic_bytes(const GemmParams& p, int z) {
+  const double mn = (double)p.M * p.N * z;
+  double b = (AM == OP_DENSE_K || AM == OP_DENSE_K2 ? 2.0 * p.M * (double)p.K * z : (double)p.a.bytes) + 2.0 * p.N * (double)p.K * z;
+  b += 2.0 * mn;
+  if (RES) b += 2.0 * mn;
+  if (p.aux) b += 2.0 * mn;
+  if constexpr (EPI == EPI_BWD || EPI == EPI_BWD_AFF) {
+    const BwdEpi& e = p.bwd;
+    if (e.res) b += 2.0 * mn / (e.res_s > 1 ? 4.0 : 1.0);
+    if (e.y) b += 2.0 * mn;
+    if (e.y2) b += 2.0 * mn;
+    if (e.bits) b += mn / 8.0;
+  }
+  return b;
 }
 
 }  // namespace vcg

@@ -11,7 +11,7 @@ enum { OP_DENSE_K = 0, OP_IM2COL = 1, OP_DGRAD = 2, OP_DENSE_MN = 3, OP_IM2COL_T
 // goes out through the LDS stage, in a round of its own
 // EPI_BWD_STREAM (fast kernel): EPI_BWD of a 1x1 conv input gradient with K <= 128 (the conv1 dgrads of layers 1-2,
 // where the epilogue's residual / y / mask operands are 4-6x the A operand): 64 x 64 tiles whose A rows AND epilogue
-// operands are DMA'd into an LDS ring several tiles ahead (igemm_fast.hip bwd_stream_body)
+// operands are DMA'd into an LDS ring several tiles ahead (bwd_stream.h bwd_stream_body)
 enum { EPI_STORE = 0, EPI_STATS = 1, EPI_SPLITK = 2, EPI_BWD = 3, EPI_BWD_AFF = 4, EPI_STORE_AUX = 5,
        EPI_BWD_STREAM = 6 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3, ACT_GELU_BWD = 4, ACT_GELU_TANH = 5, ACT_GELU_TANH_BWD = 6 };
@@ -309,6 +309,11 @@ int wide_gemm_class(const GemmParams& p);
 int wide_gemm_class_f32(const GemmParams& p);  // the fp32-residual / fp32-output class (ACT_FLAG_F32_OUT), or -1
 int run_gemm_wide(GemmParams& p, int we, hipStream_t s);
 int fast_bwd_slots(const GemmParams& p);  // partial-sum slots (grid rows) of an EPI_BWD launch of run_fast_gemm
+// conv_patch.hip: the LDS-patch kernels (layer-1 3x3 convs and their dgrads, the pair-packed stem) for a z = 1 GEMM
+// of run_fast_gemm's amode / epi: eligibility + launch (-1: not taken), and the partial-sum slots of the EPI_BWD
+// launch it would take (0: not taken)
+int run_patch_conv(const GemmParams& p, int amode, int epi, hipStream_t s);
+int patch_bwd_slots(const GemmParams& p);
 int bn_bwd_finalize_launch(const float* partial, int nb, int C, long long ld, int gx_off, float* sum_g, float* sum_gx,
                            float* dgamma, float* dbeta, int accumulate, hipStream_t s);  // grid rows (slots of EPI_BWD partials) of a fast-kernel launch
 int run_fast_wgrad(const GemmParams& p, int splits, hipStream_t s, bool dense_b = false);

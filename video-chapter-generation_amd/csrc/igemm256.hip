@@ -24,28 +24,9 @@ namespace {
 
 constexpr int G_HALF = 128 * FBK;  // elements of one operand half-tile [128][64]
 
-typedef __attribute__((address_space(3))) char g_lds_char;
-__device__ __forceinline__ uint32_t g_lds_u32(const void* p) { return (uint32_t)(uintptr_t)(const g_lds_char*)p; }
-
-// bijective remap of the launch order so that consecutive tiles (sharing A rows) run on one XCD (blocks b and b + 8
-// share an XCD): XCD x gets the contiguous tile range [x q + min(x, r), ...) of n = 8 q + r tiles
-__device__ __forceinline__ int g_xcd_tile(int b, int n) {
-  const int q = n >> 3, r = n & 7, x = b & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-
-__device__ __forceinline__ void g_unpack8(const uint4& u, float (&v)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-
 // output staging: [256][256] bf16 = 128 KiB (both operand buffers), 16-B chunk c of row r at slot c ^ (r & 15)
 __device__ __forceinline__ uint32_t g_stage_addr(const bf16_t* st, int row, int col) {
-  return g_lds_u32(st + row * 256 + 8 * ((col >> 3) ^ (row & 15)) + (col & 7));
+  return lds_u32(st + row * 256 + 8 * ((col >> 3) ^ (row & 15)) + (col & 7));
 }
 
 // profiling build (make EXTRA=-DVCG_G256_STAMPS ...): s_memtime of waves 0 and 4 of workgroup 0 at the 4 points of
@@ -68,7 +49,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;  // sub-tile rows wr * 128, cols wc * 64
   const int nx = (p.N + 255) >> 8, my = (p.M + 255) >> 8;
-  const int tile = g_xcd_tile(blockIdx.x, nx * my);
+  const int tile = xcd_range(blockIdx.x, nx * my);  // consecutive tiles (sharing A rows) on one XCD
   const int by = tile / nx, bx = tile - by * nx;
   const int m0 = by * 256, n0 = bx * 256;
   const int nk = (p.K + FBK - 1) / FBK;
@@ -323,8 +304,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         v[r] = x;
       }
       uint2 q;
-      q.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      q.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+      q.x = pack2bf(v[0], v[1]);
+      q.y = pack2bf(v[2], v[3]);
       asm volatile("ds_write_b64 %0, %1" ::"v"(g_stage_addr(st, row, col)), "v"(q) : "memory");
     }
   }
@@ -357,7 +338,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         if (Cout) *reinterpret_cast<uint4*>(Cout + (long long)m * p.ldc + n) = q[k];
         if constexpr (EPI == EPI_STATS) {
           float v[8];
-          g_unpack8(q[k], v);
+          unpack8(q[k], v);
           if (cnt == 0) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) sh[i] = v[i];

@@ -13,12 +13,12 @@
 // pipeline of igemm_fast.hip). K (pixels) is split across workgroups; every split writes an fp32
 // slab [split][M][N] that splitk_reduce_kernel sums in a fixed order (deterministic).
 #include "igemm.h"
+#include "mfma_util.h"
 
 namespace vcg {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int WBK = 64;  // pixels per k-step
@@ -29,7 +29,7 @@ constexpr int WBK = 64;  // pixels per k-step
 // bank row): XOR 0,2,4,6 over row pairs.
 template <int COLS> __device__ __forceinline__ int wswz(int row, int c) {
   if constexpr (COLS == 128) return c ^ (2 * (row & 7));
-  else return c ^ (2 * ((row >> 1) & 3));
+  else return tr_swz64(row, c);
 }
 
 // Per lane: one k-row (pixel offset `row` within the 64-pixel step) and one 16-B chunk per instruction.
@@ -145,19 +145,16 @@ template <int COLS, bool GATHER> struct MNLoader {
 // and drains it (vmcnt(0)) before every read. Ordering is explicit instead: the counted vmcnt +
 // barrier before the reads (RAW), lgkmcnt(0) + sched_barrier before the MFMAs use them, lgkmcnt(0) +
 // barrier before the stage is refilled (WAR).
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ uint32_t lds_addr(const bf16_t* p) { return (uint32_t)(uintptr_t)(const lds_char*)p; }
-
 template <int COLS> __device__ __forceinline__ void wfrag_issue(s16x4& lo, s16x4& hi, const bf16_t* lds, int r0,
                                                                 int lane, int s2) {
   const int g = lane >> 4, i = lane & 15;
   const int q = i >> 2, pp = i & 3;
   const int cl = r0 + 4 * pp;
   const int k0 = 32 * s2 + 4 * g + q, k1 = k0 + 16;
-  const uint32_t a0 = lds_addr(lds + k0 * COLS + 8 * wswz<COLS>(k0, cl >> 3) + (cl & 7));
-  const uint32_t a1 = lds_addr(lds + k1 * COLS + 8 * wswz<COLS>(k1, cl >> 3) + (cl & 7));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a0) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(a1) : "memory");
+  const uint32_t a0 = lds_u32(lds + k0 * COLS + 8 * wswz<COLS>(k0, cl >> 3) + (cl & 7));
+  const uint32_t a1 = lds_u32(lds + k1 * COLS + 8 * wswz<COLS>(k1, cl >> 3) + (cl & 7));
+  lds_tr_b16(lo, a0);
+  lds_tr_b16(hi, a1);
 }
 __device__ __forceinline__ s16x8 cat8(const s16x4& lo, const s16x4& hi) {
   return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -166,8 +163,6 @@ __device__ __forceinline__ void lgkm0() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 }
-
-__device__ __forceinline__ constexpr int wvm(int n) { return (n & 0xF) | (0x7 << 4) | (0xF << 8) | (((n >> 4) & 3) << 14); }
 
 // BG: B is the im2col gather of x (conv wgrad); !BG: B is a dense [K][ld] operand (the Linear weight gradients
 // dW = dY^T X of BERT / the head: a 1x1 "conv" whose pixels are the token rows, any column count).
@@ -218,9 +213,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     if (t + 1 < ntiles) {
       la.issue(p.a, kb + (t + 1) * WBK, ke, As + (cur ^ 1) * AE, wave);
       lb.issue(p.b, kb + (t + 1) * WBK, ke, Bs + (cur ^ 1) * BE, wave);
-      __builtin_amdgcn_s_waitcnt(wvm(NLD));
+      __builtin_amdgcn_s_waitcnt(waitcnt_vm(NLD));
     } else {
-      __builtin_amdgcn_s_waitcnt(wvm(0));
+      __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
     }
     __builtin_amdgcn_s_barrier();
     const bf16_t* Ac = As + cur * AE;
@@ -303,8 +298,6 @@ struct WPatchGeom {
   int C, CO, nct, nch, nsplit;  // channels, output channels, C / 64, (C / 64)(CO / 64), tile ranges (slabs)
 };
 
-__device__ __forceinline__ int wp_swz(int row, int c) { return c ^ (2 * ((row >> 1) & 3)); }  // = wswz<64>
-
 template <int OFF> __device__ __forceinline__ void tr_read_at(s16x4& v, uint32_t addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
 }
@@ -346,7 +339,7 @@ void wgrad3x3_patch_kernel(const bf16_t* __restrict__ x, const bf16_t* __restric
       const int pr = pix / PW, pc = pix % PW;
       const int h = h0 - 1 + pr, w = pc - 1;
       const bool ok = pix < g.NP && (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
-      const int c = wp_swz(pix, lane & 7);
+      const int c = tr_swz64(pix, lane & 7);
       const uint32_t voff =
           ok ? (uint32_t)((((long long)(img * HW + h * g.W + w)) * g.C + 64 * ci_t + 8 * c) * 2) : xbytes;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void_t*)(P + slice * 512), 16, voff, 0, 0, 0);
@@ -355,7 +348,7 @@ void wgrad3x3_patch_kernel(const bf16_t* __restrict__ x, const bf16_t* __restric
     for (int q4 = 0; q4 < KS; ++q4) {
       const int slice = wave + 4 * q4;
       const int r = 8 * slice + (lane >> 3);
-      const int c = wp_swz(r, lane & 7);
+      const int c = tr_swz64(r, lane & 7);
       const uint32_t voff =
           r < g.TM ? (uint32_t)((((long long)(img * HW + h0 * g.W + r)) * g.CO + 64 * co_t + 8 * c) * 2) : dybytes;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(yr, (lds_void_t*)(Y + slice * 512), 16, voff, 0, 0, 0);
@@ -383,8 +376,8 @@ void wgrad3x3_patch_kernel(const bf16_t* __restrict__ x, const bf16_t* __restric
   if (my > 1) issue_tile(1);
   const int cb = 16 * wave + 4 * pp;  // first input channel (within the block) of this lane's 8-B transposed read
   for (int lt = 0; lt < my; ++lt) {
-    if (lt + 1 < my) __builtin_amdgcn_s_waitcnt(wvm(NIP));
-    else __builtin_amdgcn_s_waitcnt(wvm(0));
+    if (lt + 1 < my) __builtin_amdgcn_s_waitcnt(waitcnt_vm(NIP));
+    else __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
     __builtin_amdgcn_s_barrier();
     if (lt + 2 < my) issue_tile(lt + 2);  // into the slot of tile lt - 1 (every wave is past its reads)
     const bf16_t* P = Ps + (lt % WP_RING) * PE;
@@ -396,14 +389,14 @@ void wgrad3x3_patch_kernel(const bf16_t* __restrict__ x, const bf16_t* __restric
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
         const int cl = 16 * ct + 4 * pp;
-        ya[ct][0] = lds_addr(Y + k0 * 64 + 8 * wp_swz(k0, cl >> 3) + (cl & 7));
-        ya[ct][1] = lds_addr(Y + k1 * 64 + 8 * wp_swz(k1, cl >> 3) + (cl & 7));
+        ya[ct][0] = lds_u32(Y + k0 * 64 + 8 * tr_swz64(k0, cl >> 3) + (cl & 7));
+        ya[ct][1] = lds_u32(Y + k1 * 64 + 8 * tr_swz64(k1, cl >> 3) + (cl & 7));
       }
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
         const int p0 = kpix[st][0] + kw, p1 = kpix[st][1] + kw;
-        pa[kw][0] = lds_addr(P + p0 * 64 + 8 * wp_swz(p0, cb >> 3) + (cb & 7));
-        pa[kw][1] = lds_addr(P + p1 * 64 + 8 * wp_swz(p1, cb >> 3) + (cb & 7));
+        pa[kw][0] = lds_u32(P + p0 * 64 + 8 * tr_swz64(p0, cb >> 3) + (cb & 7));
+        pa[kw][1] = lds_u32(P + p1 * 64 + 8 * tr_swz64(p1, cb >> 3) + (cb & 7));
       }
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {

@@ -22,17 +22,6 @@
 
 namespace vcg {
 
-namespace {
-
-// bijective remap of the persistent slots: XCD x (blocks b with b % 8 == x share one) takes the contiguous slot range
-// [x q + min(x, r), ...) of n = 8 q + r slots, so the tiles running at once on one XCD share A rows (and B) in its L2
-__device__ __forceinline__ int w_xcd_slot(int b, int n) {
-  const int q = n >> 3, r = n & 7, x = b & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-
-}  // namespace
-
 enum { WE_STORE = 0, WE_GELU = 1, WE_GELU_BWD = 2, WE_RES = 3, WE_RES32 = 4, WE_GELU_TANH = 5, WE_GELU_TANH_BWD = 6 };
 
 namespace {
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p) {
   const int grp = wave >> 2, wc = wave & 3;          // stagger group = M half of the tile; N quarter
   const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM, ntiles = ntn * ntm;
   const int G = gridDim.x;
-  const int slot = w_xcd_slot(blockIdx.x, G);
+  const int slot = xcd_range(blockIdx.x, G);  // the slots running at once on one XCD share A rows (and B)
   const int mine = slot < ntiles ? (ntiles - 1 - slot) / G + 1 : 0;
   const int nk = (p.K + FBK - 1) / FBK;
   const int steps = mine * nk;

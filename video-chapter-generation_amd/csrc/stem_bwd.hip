@@ -22,6 +22,7 @@
 // the slabs in a fixed order (deterministic) into the OIHW weight gradient.
 #include "bn_steps.h"
 #include "igemm.h"
+#include "mfma_util.h"
 
 #ifndef VCG_STEM_BWD_DBG
 #define VCG_STEM_BWD_DBG 0
@@ -35,29 +36,23 @@ constexpr int SB_GRID = 512;   // workgroups = slabs (two per CU)
 constexpr int SB_N = 224;      // pair-packed 7x7 taps: 7 rows x 4 super pixels x 8 (2 pixels x RGB0)
 constexpr int SB_MAXW = 112;   // conv-output width (the tile's 2W pixels are the MFMA k)
 
-typedef __attribute__((address_space(3))) char sb_lds_char;
-typedef __attribute__((address_space(3))) void lds_void_t;
-__device__ __forceinline__ uint32_t sb_addr(const bf16_t* p) { return (uint32_t)(uintptr_t)(const sb_lds_char*)p; }
-__device__ __forceinline__ void sb_tr(s16x4& v, const bf16_t* p) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(sb_addr(p)) : "memory");
-}
 // phase 1's LDS accesses are inline asm too: a plain LDS load while the next tile's LDS-DMA is in flight makes the
 // compiler drain that DMA (vmcnt(0)) first -- the overlap this kernel is built on. Ordering is explicit instead.
 typedef unsigned int sb_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int sb_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint4 sb_ld16(const void* p) {
   sb_u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(sb_addr(reinterpret_cast<const bf16_t*>(p))) : "memory");
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
   return uint4{v[0], v[1], v[2], v[3]};
 }
 __device__ __forceinline__ uint2 sb_ld8(const void* p) {
   sb_u32x2 v;
-  asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(sb_addr(reinterpret_cast<const bf16_t*>(p))) : "memory");
+  asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
   return uint2{v[0], v[1]};
 }
 __device__ __forceinline__ void sb_st16(void* p, uint4 u) {
   const sb_u32x4 v = {u.x, u.y, u.z, u.w};
-  asm volatile("ds_write_b128 %0, %1" : : "v"(sb_addr(reinterpret_cast<const bf16_t*>(p))), "v"(v) : "memory");
+  asm volatile("ds_write_b128 %0, %1" : : "v"(lds_u32(p)), "v"(v) : "memory");
 }
 __device__ __forceinline__ void sb_lgkm0() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -66,9 +61,7 @@ __device__ __forceinline__ void sb_lgkm0() {
 __device__ __forceinline__ s16x8 sb_cat(const s16x4& lo, const s16x4& hi) {
   return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
-// dy0 tile [pix][64] bf16: 16-B chunk c of pixel row r at slot c ^ 2((r >> 1) & 3) (igemm_wgrad.hip wp_swz: the
-// transposed reads of 4 consecutive rows x 16 channels are conflict-free)
-__device__ __forceinline__ int sb_swz(int row, int c) { return c ^ (2 * ((row >> 1) & 3)); }
+// (the dy0 tile [pix][64] bf16 keeps 16-B chunk c of pixel row r at slot tr_swz64(r, c))
 
 struct StemBwdArgs {
   const bf16_t* dy;      // pooled-output gradient [N][OH][OW][64]
@@ -83,7 +76,7 @@ struct StemBwdArgs {
 };
 
 // LDS slot of one tile, filled by LDS-DMA (buffer_load ... lds, 1 KiB per wave-instruction) one tile ahead:
-//   Y: the conv-output rows 2k, 2k + 1 [2W][64] bf16 in the transposed-read swizzle (sb_swz, pre-applied on the
+//   Y: the conv-output rows 2k, 2k + 1 [2W][64] bf16 in the transposed-read swizzle (tr_swz64, pre-applied on the
 //      source side), overwritten in place by dy0 in phase 1 (a thread reads and writes the same pixels and chunk);
 //   D / I: pooled gradient rows k, k + 1 [2][OW][64] bf16 and their argmax bytes [2][OW][64];
 //   P: the 9 input rows of the patch, [9][W + 4] super pixels (zeros outside the frame, from the DMA range check).
@@ -162,7 +155,7 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
     for (int i = wave; i < nDMA; i += SB_NTH / 64) {
       if (i < nY) {
         const int pix = 8 * i + (lane >> 3), aa = pix >= W, w = pix - aa * W;
-        const int c = sb_swz(pix, lane & 7);  // the chunk that lands at slot lane & 7 (XOR: its own inverse)
+        const int c = tr_swz64(pix, lane & 7);  // the chunk that lands at slot lane & 7 (XOR: its own inverse)
         const uint32_t voff = (uint32_t)(((((long long)n * H + 2 * k + aa) * W + w) * 64 + 8 * c) * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(yr, (lds_void_t*)(S + 1024 * i), 16, voff, 0, 0, 0);
       } else if (i < nY + nD) {
@@ -205,7 +198,7 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
 #pragma unroll
       for (int p4 = 0; p4 < 4; ++p4) {
         const int pix = (p4 >> 1) * W + 2 * jj + (p4 & 1);
-        y4s[p4] = sb_ld16(Y + pix * 64 + 8 * sb_swz(pix, c8));
+        y4s[p4] = sb_ld16(Y + pix * 64 + 8 * tr_swz64(pix, c8));
       }
       sb_lgkm0();
     }
@@ -213,7 +206,7 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
     for (int p4 = 0; p4 < 4; ++p4) {
       const int aa = p4 >> 1, cc = p4 & 1;
       const int pix = aa * W + 2 * jj + cc;
-      bf16_t* yp = Y + pix * 64 + 8 * sb_swz(pix, c8);
+      bf16_t* yp = Y + pix * 64 + 8 * tr_swz64(pix, c8);
       const uint4 y4 = y4s[p4];
       float acc[8], yv[8];
 #pragma unroll
@@ -248,7 +241,7 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
           const float gr = bf2f(f2bf(v));  // the gradient as maxpool_bwd_kernel stores / recomputes it
           d[h] = bn_bwd_map(a.train, A[e + h], Bc[e + h], Cc[e + h], gr, yv[e + h]);
         }
-        o[e >> 1] = (uint32_t)f2bf(d[0]) | ((uint32_t)f2bf(d[1]) << 16);
+        o[e >> 1] = pack2bf(d[0], d[1]);
       }
       sb_st16(yp, uint4{o[0], o[1], o[2], o[3]});
     }
@@ -282,16 +275,16 @@ void stem_bwd_fused_kernel(StemBwdArgs a) {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int cl = 32 * wm + 16 * mt + 4 * pp;  // this lane's channels in the dy0 transposed read
-        sb_tr(al[b][mt], dyT + k0 * 64 + 8 * sb_swz(k0, cl >> 3) + (cl & 7));
-        sb_tr(ah[b][mt], dyT + k1 * 64 + 8 * sb_swz(k1, cl >> 3) + (cl & 7));
+        lds_tr_b16(al[b][mt], dyT + k0 * 64 + 8 * tr_swz64(k0, cl >> 3) + (cl & 7));
+        lds_tr_b16(ah[b][mt], dyT + k1 * 64 + 8 * tr_swz64(k1, cl >> 3) + (cl & 7));
       }
       const int a0 = k0 >= W, a1 = k1 >= W;
       const int ow0 = min(k0 - a0 * W, W - 1), ow1 = min(k1 - a1 * W, W - 1);  // (pad pixels: any in-bounds chunk)
 #pragma unroll
       for (int u = 0; u < 7; ++u) {
         const int t = 7 * wn + u, kh = t >> 1, kwp = 2 * (t & 1) + (pp >> 1), e0 = 4 * (pp & 1);
-        sb_tr(bl[b][u], P + ((2 * a0 + kh) * SPW + ow0 + kwp) * 8 + e0);
-        sb_tr(bh[b][u], P + ((2 * a1 + kh) * SPW + ow1 + kwp) * 8 + e0);
+        lds_tr_b16(bl[b][u], P + ((2 * a0 + kh) * SPW + ow0 + kwp) * 8 + e0);
+        lds_tr_b16(bh[b][u], P + ((2 * a1 + kh) * SPW + ow1 + kwp) * 8 + e0);
       }
     };
     auto step = [&](int s, int b) {

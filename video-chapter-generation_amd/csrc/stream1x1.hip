@@ -16,6 +16,7 @@
 //
 // Same products, summation order and roundings as epilogue_staged_res (bit-identical out and bits).
 #include "igemm.h"
+#include "mfma_util.h"
 
 namespace vcg {
 namespace {
@@ -29,11 +30,10 @@ __device__ __forceinline__ int rswz(int row, int chunk) { return chunk ^ ((row >
 // element j of lane 16g+i is k = 32 s2 + 8g + j)
 // (inline asm: a plain LDS load of the loop-invariant weights would be hoisted out of the tile loop by the
 // compiler -- every fragment of the 256 x K block held in registers, spilled)
-typedef __attribute__((address_space(3))) char rs_lds_t;
 __device__ __forceinline__ s16x8 rs_bfrag(const bf16_t* Bkt, int r0, int lane, int s2) {
   const int g = lane >> 4, i = lane & 15;
   const int row = r0 + i;
-  const uint32_t addr = (uint32_t)(uintptr_t)(const rs_lds_t*)(Bkt + row * 64 + 8 * rswz(row, 4 * s2 + g));
+  const uint32_t addr = lds_u32(Bkt + row * 64 + 8 * rswz(row, 4 * s2 + g));
   s16x8 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
   return v;
@@ -58,15 +58,6 @@ __device__ __forceinline__ void rs_load(RsTile<K>& t, const bf16_t* __restrict__
   for (int s = 0; s < K / 32; ++s) t.a[s] = *reinterpret_cast<const uint4*>(X + m * K + 32 * s + 8 * g);
 #pragma unroll
   for (int p = 0; p < RS_TN / 32; ++p) t.r[p] = *reinterpret_cast<const uint4*>(R + m * N + n0 + rs_col(p, g));
-}
-
-__device__ __forceinline__ void unpack8s(const uint4& u, float (&v)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
 }
 
 template <int K>
@@ -116,18 +107,15 @@ __device__ __forceinline__ void rs_compute(const RsTile<K>& t, const bf16_t* Bs,
       }
       const uint4 cv = make_uint4(vw[0][0], vw[0][1], vw[1][0], vw[1][1]);  // columns rs_col(p, g) .. + 7
       float a8[8], r8[8];
-      unpack8s(cv, a8);
-      unpack8s(t.r[p], r8);
+      unpack8(cv, a8);
+      unpack8(t.r[p], r8);
       uint32_t byte = 0;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         a8[e] = fmaxf(a8[e] + r8[e], 0.f);
         byte |= (a8[e] > 0.f ? 1u : 0u) << e;
       }
-      const uint4 o = make_uint4((uint32_t)f2bf(a8[0]) | ((uint32_t)f2bf(a8[1]) << 16),
-                                 (uint32_t)f2bf(a8[2]) | ((uint32_t)f2bf(a8[3]) << 16),
-                                 (uint32_t)f2bf(a8[4]) | ((uint32_t)f2bf(a8[5]) << 16),
-                                 (uint32_t)f2bf(a8[6]) | ((uint32_t)f2bf(a8[7]) << 16));
+      const uint4 o = pack8(a8);
       if (ok) *reinterpret_cast<uint4*>(out + m * N + n0 + rs_col(p, g)) = o;
       mb[p >> 2] |= byte << (8 * (p & 3));  // this lane's byte of pair p: row byte 4p + (0, 2, 1, 3)[g]
     }

@@ -18,6 +18,7 @@
 #define VCG_HIP_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vcg_gpt_decode.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -475,6 +476,48 @@ VCG_API int vcg_listnet_fwd(int dtype, const void* P, const float* targets, cons
 /* One launch: dP (fp32 [B S][H], every row written exactly once) for the upstream scalar dloss[0] (device);
    dW [2][H] and db [2] (both or neither NULL) are ADDED to, in the order of m. No atomics; duplicate sel add. */
 VCG_API int vcg_listnet_bwd(int dtype, const void* P, const float* targets, const long long* sel, const long long* cls, const float* W, const float* p, const float* prob, const float* dloss, int B, int S, int H, int M, float* dP, float* dW, float* db, hipStream_t stream);
+
+/* ---- GPT text generation on a KV cache (gpt_decode.hip): what train_lang/test_gpt_hugface.py does with the
+ *      generative stage's checkpoint through common_utils/language_model_utils.py:token_idx_sample (temperature, top-k,
+ *      multinomial), which re-runs the decoder on the whole prefix per token. Here K and V are cached per layer, one
+ *      query row per sequence attends over the cache, and the next token is chosen on the device. Fixed reduction
+ *      orders, no floating-point atomics: bit-identical run to run. -------------------------------------------------- */
+/* Decode attention with cache append. qkv_new [B][3 nh dh] (this step's fused QKV projection), kcache / vcache
+   [B][nh][Tcap][dh] in `dtype`, len0 DEVICE int32 [B], t the host step index. For sequence b and head h: K and V of
+   position p = len0[b] + t are stored (bit copies of the qkv_new slices), and ctx[b][h] = softmax(scale q K[0..p]) V[0..p]
+   (fp32 accumulation). Causal by construction; no mask: the prompt is a valid prefix. dh must be 64
+   (VCG_ERR_UNSUPPORTED); max_len0 + t >= Tcap is VCG_ERR_INVALID (max_len0 = the host's max of len0; a device len0
+   beyond it makes its sequence write nothing). One workgroup per (b, h), keys split over its waves, K / V straight to
+   registers. */
+VCG_API int vcg_attn_decode(int dtype, const void* qkv_new, void* kcache, void* vcache, const int* len0, int max_len0, int t, void* ctx, int B, int nh, int dh, int Tcap, float scale, hipStream_t s);
+/* Fused sampler, one workgroup per row of fp32 logits [B][ldz] (V valid columns; the pad columns are never read):
+   z = logits / temperature (> 0); top_k 0 = no cut, else 1..V: every entry >= the k-th largest stays (ties at the k-th
+   value all kept, as language_model_utils.top_k_logits' `out[out < v[:, [-1]]] = -inf`; the cut is made on the logits,
+   whose order the division keeps); softmax over the kept set (exp in fp32, sums in double, index order); the token is
+   the first kept index whose running sum exceeds u[b] * total, u in [0, 1). greedy: the argmax, lowest index on equal
+   values (u may be NULL). Outputs, each optional (seq or chosen must be given): chosen[b * chosen_ld] = the token;
+   prob[b] = its probability under the kept set (greedy: 1); seq [B][Tcap] int64: column (len0 ? len0[b] : 0) + col_off
+   receives forced[b * forced_ld] when forced is given (teacher forcing), else the token. max_len0 + col_off >= Tcap is
+   VCG_ERR_INVALID. */
+VCG_API int vcg_sample_topk(const float* logits, long long ldz, int B, int V, float temperature, int top_k, int greedy, const float* u, long long* seq, int Tcap, const int* len0, int max_len0, int col_off, const long long* forced, long long forced_ld, long long* chosen, long long chosen_ld, float* prob, hipStream_t s);
+/* vcg_gpt_embed_fwd for one position per sequence, read from device memory: out[b] = tok[seq[b][p]] + pos[p],
+   p = len0[b] + t (no dropout). max_len0 + t must be below Tcap and n_pos (VCG_ERR_INVALID). */
+VCG_API int vcg_gpt_embed_at(int dtype, const long long* seq, int Tcap, const int* len0, int max_len0, int t, const float* tok, const float* pos, void* out, int B, int H, int V, int n_pos, hipStream_t s);
+/* One token of the whole decoder, enqueued from C (vcg_gpt_decode.h: the descriptor): embedding of position len0 + t,
+   per layer QKV -> vcg_attn_decode -> projection -> LayerNorm -> FFN1 + tanh-GELU -> FFN2 -> LayerNorm on vcg_gemm /
+   vcg_ln_fwd, the vocabulary head, then vcg_sample_topk with row t + 1 of u / forced / chosen / prob into column
+   len0 + t + 1 of seq (row 0 and column len0 belong to the prompt's own forward). t in 0..steps-2. Nothing is read
+   back; every refusal is made before the first launch. */
+/* Skinny GEMM, bf16, M <= 16 (a decode step's Linear layers and vocabulary head): y[M][N] = act(x[M][K] W[N][K]^T + b),
+   x and W K-contiguous and 16-B aligned, K a multiple of 32, any N; y bf16, or fp32 with f32_out (act none); act
+   VCG_ACT_NONE or VCG_ACT_GELU_TANH (of the unrounded value); bias may be NULL; ldc = row pitch of y. The weights go
+   straight from memory to the registers of a 16x16x32 MFMA (deep unroll, late wait, no LDS staging), K is split over
+   the four waves of a workgroup and summed through LDS in a fixed order: deterministic. A workgroup owns 16 columns,
+   or 8 / 4 where that is what fills half the CUs (N = 768: 192 workgroups). M > 16 is VCG_ERR_INVALID. Census key
+   "gemm_skinny". */
+VCG_API int vcg_gemm_skinny(const void* x, const void* W, const float* bias, void* y, int M, int N, int K, long long ldc, int act, int f32_out, hipStream_t s);
+VCG_API long long vcg_gpt_decode_desc_bytes(void);
+VCG_API int vcg_gpt_decode_step(const vcg_gpt_decode_desc* d, int t, hipStream_t s);
 
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148

@@ -17,6 +17,7 @@ diverge from transformers (which lets them attend to future valid keys); right p
 import logging
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -115,6 +116,105 @@ class GPTHugface(NativeRoot, nn.Module):
             return (torch.full((), float("nan"), device=dev, requires_grad=torch.is_grad_enabled()),
                     torch.zeros((), dtype=torch.int64, device=dev), 0)
         return self._fused_loss(self._last_hidden(x, attention_mask), rows, tgt)
+
+    # generate(): draw the tokens whose context fits block_size on the KV cache (vcg_hip/gpt_decode.py); False: every
+    # token re-runs the forward on its window, the reference's algorithm (tests and tools compare both)
+    use_kv_cache = True
+
+    @torch.no_grad()
+    def generate(self, x, attention_mask=None, steps=1, temperature=1.0, sample=False, top_k=None, block_size=None,
+                 generator=None, forced=None):
+        """Text generation, the reference's common_utils/language_model_utils.py:token_idx_sample (temperature, top-k,
+        multinomial or argmax) for a right-padded batch: x [B, L] token ids, attention_mask [B, L] (None: all ones;
+        each row a prefix of ones with at least one token -- left padding, holes and empty rows are a ValueError).
+        Returns (seq [B, max(len0) + steps] int64: row b holds its prompt and then its `steps` new tokens, zeros behind;
+        new_tokens [B, steps]).
+
+        The model is put in eval mode, as the reference does. While the context the model sees stays within block_size
+        (default: the position table) the tokens are drawn on the KV cache (vcg_hip/gpt_decode.py: one enqueued chain
+        per token, the next token chosen on the device, no host synchronisation). Beyond it the reference slides the
+        window, x[:, -block_size:], which shifts every learned position: the cache is invalid there, so those tokens
+        re-run the native forward on the cropped window and apply the sampler kernel to its last row
+        (plan_generation says how many of each).
+
+        sample=True draws by inverse CDF, in vocabulary order over the kept set, from uniforms made once by
+        torch.rand((steps, B), generator=generator): reproducible for a seeded generator, but NOT torch.multinomial's
+        random stream -- the tokens differ from the reference's for the same seed, their distribution does not.
+        forced [B, steps] (tests): teacher forcing -- new_tokens still holds the sampler's choice, but the forced
+        token is what is written to seq and fed back."""
+        from vcg_hip import gpt_decode as gd
+        from vcg_hip.mlm import _head_weights
+        if not self._is_vocab_head():
+            raise RuntimeError("generate needs the vocabulary head (build_chapter_head replaced it)")
+        if x.dim() != 2 or not x.is_cuda:
+            raise ValueError("generate: x must be a [B, L] GPU tensor of token ids (there is no CPU path)")
+        B, L = x.shape
+        dev = x.device
+        n_pos = self.base_model.config.n_positions
+        block = n_pos if block_size is None else int(block_size)
+        if not 1 <= block <= n_pos:
+            raise ValueError(f"generate: block_size {block} outside 1..n_positions = {n_pos}")
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("generate: steps must be at least 1")
+        mask_np = (np.ones((B, L), dtype=np.int64) if attention_mask is None
+                   else attention_mask.detach().cpu().numpy())
+        if mask_np.shape != (B, L):
+            raise ValueError(f"attention_mask {mask_np.shape} does not match x {(B, L)}")
+        lens = gd.check_prefix_mask(mask_np)
+        if forced is not None and tuple(forced.shape) != (B, steps):
+            raise ValueError("generate: forced must be [B, steps]")
+        cached, sliding = gd.plan_generation(lens, steps, block)
+        if not GPTHugface.use_kv_cache:
+            cached, sliding = 0, steps
+        self.eval()
+        greedy = not sample
+        u = None
+        if sample:
+            gdev = generator.device if generator is not None else "cpu"
+            u = torch.rand((steps, B), generator=generator, device=gdev).to(dev, torch.float32)
+        if forced is not None:
+            forced = forced.to(dev, torch.int64).contiguous()
+        max_len0 = int(lens.max())
+        W = max_len0 + steps
+        seq = torch.zeros((B, W), dtype=torch.int64, device=dev)
+        mask_dev = torch.from_numpy(mask_np).to(dev)
+        seq[:, :L] = (x * mask_dev)[:, :W]
+        new_tokens = torch.zeros((B, steps), dtype=torch.int64, device=dev)
+        len0_dev = torch.from_numpy(lens.astype(np.int32)).to(dev)
+        if cached:
+            dec = getattr(self, "_vcg_decoder", None)
+            if dec is None or dec.cap != block or dec.dtype != self.compute_dtype():
+                dec = gd.GptDecoder(self, block)
+                object.__setattr__(self, "_vcg_decoder", dec)
+            dec.prefill(x, attention_mask, steps=cached, temperature=temperature, top_k=top_k or 0, greedy=greedy,
+                        u=None if u is None else u[:cached], forced=None if forced is None else forced[:, :cached])
+            for t in range(cached - 1):
+                dec.step(t)
+            wc = min(W, dec.Tcap)
+            seq[:, :wc] = dec.seq[:, :wc]  # (the one copy of the finished token matrix)
+            new_tokens[:, :cached] = dec.chosen
+        if sliding:
+            head_w = None
+            for g in range(cached, steps):
+                cur = lens + g                      # each sequence's length before token g
+                start = np.maximum(0, cur - block)  # its window: the last `block` tokens
+                wl = cur - start
+                Lw = int(wl.max())
+                cols = start[:, None] + np.arange(Lw)[None, :]
+                wmask = torch.from_numpy((np.arange(Lw)[None, :] < wl[:, None]).astype(np.int64)).to(dev)
+                ids = seq.gather(1, torch.from_numpy(np.minimum(cols, W - 1)).to(dev)) * wmask
+                last = self._last_hidden(ids, wmask)
+                if head_w is None:
+                    Wd, Wp = _head_weights(self, self.head, last.dtype)
+                    head_w = Wd if Wp is None else Wp
+                rows = torch.from_numpy((np.arange(B) * Lw + wl - 1).astype(np.int64)).to(dev)
+                logits = gd.head_logits(last.index_select(0, rows), head_w)
+                gd.sample(logits, self.vocab_size, temperature, top_k or 0, greedy, None if u is None else u[g],
+                          seq=seq, len0=len0_dev, max_len0=max_len0, col_off=g,
+                          forced=None if forced is None else forced[:, g:], forced_ld=steps,
+                          chosen=new_tokens[:, g:], chosen_ld=steps)
+        return seq, new_tokens
 
     def forward(self, x, attention_mask=None, targets=None):
         """gpt_hugface.py:82-101: (logits [B, L, V] fp32, autograd-connected; loss = the mean cross-entropy over the

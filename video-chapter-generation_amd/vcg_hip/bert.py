@@ -317,9 +317,10 @@ class BertEncoderEngine:
         return (BertEncoderEngine.unpad and self.pooled_only and arch.pooler is not None and ids.is_cuda
                 and self._fused_attn(ids.shape[1], arch.H // arch.nh))
 
-    def forward(self, ids, mask, need_grad, seed, packing=None):
+    def forward(self, ids, mask, need_grad, seed, packing=None, kv_sink=None):
         """packing: a Packing or PackingRequest of `mask` (only where packs()); its kept rows are computed, and the
-        second output (the last hidden state) is then empty."""
+        second output (the last hidden state) is then empty. kv_sink(i, qkv_buf): called with each layer's fused QKV
+        projection output [rows (+8), 3H] (vcg_hip/gpt_decode.py fills its K / V caches from it)."""
         m, dt, flat, arch = self.m, self.dtype, self.flat, self.arch
         if packing is None:
             packing = self.packing
@@ -366,6 +367,8 @@ class BertEncoderEngine:
             qkv_buf = torch.empty((rows + 8, 3 * H), dtype=dt, device=dev)  # +8 rows: padded key reads
             qkv = qkv_buf[:rows]
             self._lin_fwd(lq, h, rows, out=qkv, ldc=3 * H)
+            if kv_sink is not None:
+                kv_sink(i, qkv_buf)
             sa = _seed(seed, i + 1, 1)
             ctx, att = attention_fwd(qkv_buf, att_mask, B, nh, L, Lp, dh, scale, p_a, sa, self._fused_attn(L, dh),
                                      seq=seq, rows=rows, causal=arch.causal)

@@ -519,6 +519,25 @@ VCG_API int vcg_gemm_skinny(const void* x, const void* W, const float* bias, voi
 VCG_API long long vcg_gpt_decode_desc_bytes(void);
 VCG_API int vcg_gpt_decode_step(const vcg_gpt_decode_desc* d, int t, hipStream_t s);
 
+/* ---- Pegasus chapter titles, inference (pegasus.hip): transformers PegasusForConditionalGeneration as the reference's
+ *      model/lang/pegasus_hugface.py uses it. Fixed reduction orders, no floating-point atomics. -------------------- */
+/* Cross-attention forward: ctx[b, i] = softmax_j(scale q[b, i] . k[b, j] + mask) v[b, j] per head. q [B*Lq][ldq] (the
+   decoder's query projection, H = nh * 64 columns used), kv [B*Lk][ldkv] with K in columns 0..H-1 and V in H..2H-1
+   (one layer's key / value projection of the encoder output; rows behind B*Lk are never read), key_mask int64 [B][Lk]
+   (NULL: every key valid), ctx [B*Lq][H], stats fp32 [B*nh][Lq][2] = (row maximum of the scaled scores over the valid
+   keys, row sum of exp(score - maximum)) or NULL. Any Lq >= 1 and Lk >= 1. A sequence without any valid key attends
+   uniformly to all its Lk keys (HF's result for a fully masked row); its stats are (-inf, Lk). dh must be 64
+   (VCG_ERR_INVALID, nothing written). bf16: one workgroup of 4 waves per (sequence, head, 16-query tile) on
+   mfma_f32_16x16x32_bf16, the keys dealt to the waves in strips of 32, an online softmax per wave, the four partials
+   combined through LDS in a fixed order; K and V are read once per workgroup and nothing Lq x Lk goes to HBM
+   (ldq, ldkv multiples of 8; q, kv, ctx 16-B aligned). fp32: a plain kernel for the parity mode. No dropout:
+   inference. */
+VCG_API int vcg_cross_attn_kv_fwd(int dtype, const void* q, long long ldq, const void* kv, long long ldkv, const long long* key_mask, void* ctx, float* stats, int B, int nh, int dh, int Lq, int Lk, float scale, hipStream_t s);
+/* Pegasus' embedding: out[b, t] = scale * tok[ids[b, t]] + pos[pos0 + t] (tok fp32 [V][H], pos fp32 [n_pos][H], out
+   [B*L][H] in `dtype`), the arithmetic in double and one rounding to fp32 before the storage dtype. pos0 + L > n_pos
+   is VCG_ERR_INVALID. */
+VCG_API int vcg_pegasus_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B, int L, int H, int V, int n_pos, float scale, int pos0, hipStream_t s);
+
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148
  * (bucketed gradient all-reduce on every backward) and the parameter broadcast of :261-263. One communicator per

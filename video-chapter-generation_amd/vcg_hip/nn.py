@@ -121,8 +121,19 @@ def _flat_order(names):
                     out.append(g)
                     seen.add(g)
             continue
-        out.append(n)
-        seen.add(n)
+        # Pegasus (module order k, v, q): the self-attention's q | k | v and the cross-attention's k | v back to back
+        for suffix, members in (("self_attn.k_proj.weight", ("q_proj", "k_proj", "v_proj")),
+                                ("encoder_attn.k_proj.weight", ("k_proj", "v_proj"))):
+            if n.endswith(suffix):
+                pre = n[: -len("k_proj.weight")]
+                for g in [pre + m + ".weight" for m in members] + [pre + m + ".bias" for m in members]:
+                    if g in names and g not in seen:
+                        out.append(g)
+                        seen.add(g)
+                break
+        else:
+            out.append(n)
+            seen.add(n)
     return out
 
 
@@ -475,6 +486,152 @@ class OpenAIGPTModel(NativeRoot, nn.Module):
                                       "nothing else)")
         B, L = input_ids.shape
         return GPTOutput(self.native_forward(input_ids, attention_mask).view(B, L, -1))
+
+
+# ============================================================================ Pegasus
+class PegasusConfig:
+    """The subset of transformers.PegasusConfig the model uses (google/pegasus-large defaults)."""
+
+    def __init__(self, vocab_size=96103, d_model=1024, encoder_layers=16, decoder_layers=16,
+                 encoder_attention_heads=16, decoder_attention_heads=16, encoder_ffn_dim=4096, decoder_ffn_dim=4096,
+                 max_position_embeddings=1024, activation_function="relu", scale_embedding=True, pad_token_id=0,
+                 eos_token_id=1, decoder_start_token_id=0, dropout=0.1, attention_dropout=0.1, activation_dropout=0.1,
+                 layer_norm_eps=1e-5, init_std=0.02, **kwargs):
+        self.vocab_size = vocab_size
+        self.d_model = d_model
+        self.encoder_layers = encoder_layers
+        self.decoder_layers = decoder_layers
+        self.encoder_attention_heads = encoder_attention_heads
+        self.decoder_attention_heads = decoder_attention_heads
+        self.encoder_ffn_dim = encoder_ffn_dim
+        self.decoder_ffn_dim = decoder_ffn_dim
+        self.max_position_embeddings = max_position_embeddings
+        self.activation_function = activation_function
+        self.scale_embedding = scale_embedding
+        self.pad_token_id = pad_token_id
+        self.eos_token_id = eos_token_id
+        self.decoder_start_token_id = decoder_start_token_id
+        self.dropout = dropout
+        self.attention_dropout = attention_dropout
+        self.activation_dropout = activation_dropout
+        self.layer_norm_eps = layer_norm_eps
+        self.init_std = init_std
+        for k, v in kwargs.items():
+            setattr(self, k, v)
+
+    hidden_size = property(lambda self: self.d_model)
+
+
+def pegasus_sinusoidal_table(n_pos, dim):
+    """transformers' PegasusSinusoidalPositionalEmbedding.create_weight: sin in columns [0, dim/2), cos behind them (not
+    interleaved), computed in float64 and rounded to fp32."""
+    import numpy as np
+    j = np.arange(dim)
+    enc = np.arange(n_pos)[:, None] / np.power(10000, 2 * (j // 2) / dim)[None, :]
+    out = torch.empty(n_pos, dim, dtype=torch.float32)
+    sentinel = dim // 2 if dim % 2 == 0 else dim // 2 + 1
+    out[:, :sentinel] = torch.from_numpy(np.sin(enc[:, 0::2])).float()
+    out[:, sentinel:] = torch.from_numpy(np.cos(enc[:, 1::2])).float()
+    return out
+
+
+class _PegasusAttention(nn.Module):
+    def __init__(self, d):
+        super().__init__()
+        self.k_proj = nn.Linear(d, d)
+        self.v_proj = nn.Linear(d, d)
+        self.q_proj = nn.Linear(d, d)
+        self.out_proj = nn.Linear(d, d)
+
+
+class _PegasusLayer(nn.Module):
+    def __init__(self, d, ffn, eps, cross):
+        super().__init__()
+        self.self_attn = _PegasusAttention(d)
+        self.self_attn_layer_norm = nn.LayerNorm(d, eps=eps)
+        if cross:
+            self.encoder_attn = _PegasusAttention(d)
+            self.encoder_attn_layer_norm = nn.LayerNorm(d, eps=eps)
+        self.fc1 = nn.Linear(d, ffn)
+        self.fc2 = nn.Linear(ffn, d)
+        self.final_layer_norm = nn.LayerNorm(d, eps=eps)
+
+
+class _PegasusStack(nn.Module):
+    def __init__(self, c, shared, n_layers, ffn, cross):
+        super().__init__()
+        self.embed_tokens = shared
+        self.embed_positions = nn.Embedding(c.max_position_embeddings, c.d_model)
+        self.embed_positions.weight.requires_grad = False
+        self.layers = nn.ModuleList([_PegasusLayer(c.d_model, ffn, c.layer_norm_eps, cross) for _ in range(n_layers)])
+        self.layer_norm = nn.LayerNorm(c.d_model, eps=c.layer_norm_eps)
+
+
+class _PegasusModel(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.shared = nn.Embedding(c.vocab_size, c.d_model, padding_idx=c.pad_token_id)
+        self.encoder = _PegasusStack(c, self.shared, c.encoder_layers, c.encoder_ffn_dim, cross=False)
+        self.decoder = _PegasusStack(c, self.shared, c.decoder_layers, c.decoder_ffn_dim, cross=True)
+
+
+class PegasusForConditionalGeneration(NativeRoot, nn.Module):
+    """transformers.PegasusForConditionalGeneration (the reference's model/lang/pegasus_hugface.py:23) with its
+    state-dict keys -- `final_logits_bias`, `model.shared`, `model.{encoder,decoder}.embed_tokens` (tied to `shared`),
+    `embed_positions` (the sinusoidal table: not trained, a checkpoint may overwrite it), `layers.{i}.self_attn.
+    {k,v,q,out}_proj`, `self_attn_layer_norm`, `encoder_attn*` (decoder), `fc1`, `fc2`, `final_layer_norm`,
+    `layer_norm`, `lm_head` (tied to `shared`) -- executed by vcg_hip/pegasus.py's PegasusEngine: pre-LayerNorm
+    blocks, ReLU, fused self- and cross-attention. Inference only (eval mode).
+
+    Not implemented (NotImplementedError): an activation other than relu, a head dim other than 64, a nonzero
+    final_logits_bias (pegasus-large's is all zero)."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = config if config is not None else PegasusConfig()
+        c = self.config
+        if c.activation_function != "relu":
+            raise NotImplementedError(f"native Pegasus implements activation_function='relu', not "
+                                      f"{c.activation_function!r}")
+        for what, nh in (("encoder", c.encoder_attention_heads), ("decoder", c.decoder_attention_heads)):
+            if c.d_model != 64 * nh:
+                raise NotImplementedError(f"native Pegasus needs head dim 64: d_model {c.d_model} with {nh} {what} "
+                                          "heads")
+        self.model = _PegasusModel(c)
+        self.lm_head = nn.Linear(c.d_model, c.vocab_size, bias=False)
+        self.lm_head.weight = self.model.shared.weight
+        self.register_buffer("final_logits_bias", torch.zeros(1, c.vocab_size))
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                if m.weight is not self.model.shared.weight:
+                    nn.init.normal_(m.weight, 0.0, c.init_std)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.LayerNorm):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+        with torch.no_grad():
+            nn.init.normal_(self.model.shared.weight, 0.0, c.init_std)
+            self.model.shared.weight[c.pad_token_id].zero_()
+            for st in (self.model.encoder, self.model.decoder):
+                st.embed_positions.weight.copy_(pegasus_sinusoidal_table(c.max_position_embeddings, c.d_model))
+
+    def check_supported(self):
+        """After loading a checkpoint: the head's additive bias must be zero (it is not applied)."""
+        if bool((self.final_logits_bias != 0).any()):
+            raise NotImplementedError("native Pegasus: final_logits_bias is not all zero")
+
+    def check_text_len(self, L, what="text"):
+        P = self.config.max_position_embeddings
+        if L > P:
+            raise ValueError(f"Pegasus: {what} length {L} exceeds max_position_embeddings {P}")
+
+    def engine(self, root=None):
+        """The PegasusEngine of this model on the flat buffers of `root` (the module that owns the parameters: this
+        one, or a wrapper such as model.lang.pegasus_hugface.PegasusHugface)."""
+        from .pegasus import PegasusEngine
+        flat = (root if root is not None else self).native_flat()
+        return PegasusEngine(self, flat, self.compute_dtype())
 
 
 def check_max_text_len(model, max_text_len):

@@ -771,6 +771,43 @@ def gpt_embed_bwd(dout, ids, tok_grad, pos_grad, B, L, H, p=0.0, seed=0, storage
               float(p), int(seed) & (2**64 - 1), stream())
 
 
+def pegasus_embed_fwd(ids, tok, pos, B, L, H, dtype, scale, pos0=0):
+    """Pegasus' embedding: scale * tok[ids] + pos[pos0 + t] -> [B*L, H] (fp32 tables, one rounding)."""
+    _chk(ids, torch.int64, "ids")
+    _chk(tok, torch.float32, "tok")
+    _chk(pos, torch.float32, "pos")
+    out = torch.empty((B * L, H), dtype=dtype, device=ids.device)
+    _lib.call("vcg_pegasus_embed_fwd", dt_code(dtype), P(ids), P(tok), P(pos), P(out), B, L, H, tok.shape[0],
+              pos.shape[0], float(scale), int(pos0), stream())
+    return out
+
+
+def cross_attn_kv_fwd(q, kv, key_mask, B, nh, Lq, Lk, scale, ctx=None, stats=None, dh=64):
+    """Fused cross-attention forward (csrc/pegasus.hip): q [B*Lq, ldq], kv [B*Lk (+pad), ldkv] = K | V, key_mask int64
+    [B, Lk] or None -> ctx [B*Lq, nh*dh]; stats (optional fp32 [B*nh, Lq, 2]) receives (row max, row sum)."""
+    for t, name in ((q, "q"), (kv, "kv")):  # (row-major with any row pitch: column slices of a fused buffer are fine)
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype:
+            raise RuntimeError(f"{name} must be a 2-D GPU tensor with unit column stride, in q's dtype")
+    if q.shape[0] < B * Lq or kv.shape[0] < B * Lk or q.shape[1] < nh * dh or kv.shape[1] < 2 * nh * dh:
+        raise ValueError(f"cross_attn_kv_fwd: q {tuple(q.shape)} / kv {tuple(kv.shape)} too small for B={B} nh={nh} "
+                         f"Lq={Lq} Lk={Lk}")
+    if key_mask is not None:
+        _chk(key_mask, torch.int64, "key_mask")
+        if key_mask.numel() < B * Lk:
+            raise ValueError("cross_attn_kv_fwd: key_mask smaller than [B, Lk]")
+    if ctx is not None and (ctx.numel() < B * Lq * nh * dh or ctx.dtype != q.dtype):
+        raise ValueError("cross_attn_kv_fwd: ctx must be [B*Lq, nh*dh] in q's dtype")
+    if stats is not None and stats.numel() < 2 * B * nh * Lq:
+        raise ValueError("cross_attn_kv_fwd: stats smaller than [B*nh, Lq, 2]")
+    if ctx is None:
+        ctx = torch.empty((B * Lq, nh * dh), dtype=q.dtype, device=q.device)
+    if stats is not None:
+        _chk(stats, torch.float32, "stats")
+    _lib.call("vcg_cross_attn_kv_fwd", dt_code(q.dtype), P(q), q.stride(0), P(kv), kv.stride(0), P(key_mask), P(ctx),
+              P(stats), B, nh, dh, Lq, Lk, float(scale), stream())
+    return ctx
+
+
 def attn_softmax_fwd(S, mask, P_out, Pd_out, B, nh, L, Lp, scale, p=0.0, seed=0, causal=False):
     if causal:
         _lib.call("vcg_attn_softmax_fwd_ex", dt_code(S.dtype), P(S), P(mask), P(P_out), P(Pd_out), B, nh, L, Lp,

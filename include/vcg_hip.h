@@ -538,6 +538,47 @@ VCG_API int vcg_cross_attn_kv_fwd(int dtype, const void* q, long long ldq, const
    is VCG_ERR_INVALID. */
 VCG_API int vcg_pegasus_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B, int L, int H, int V, int n_pos, float scale, int pos0, hipStream_t s);
 
+/* ---- Pegasus chapter titles, training kernels (pegasus.hip; the embedding backward in bert.hip). Dropout is
+ *      dropout_keep of the library (tests/dropout_util.py restates it) with the counter spaces given per entry; every
+ *      reduction has a fixed order and there is no floating-point atomic: results are bit-identical run to run. ------ */
+/* vcg_cross_attn_kv_fwd with dropout on P: P[z = b * nh + h][q][k] is dropped at counter (z * Lq + q) * Lk + k and the
+   kept ones scaled by 1 / (1 - dropout_p); the statistics are those of the undropped row. dropout_p = 0 runs
+   vcg_cross_attn_kv_fwd's kernels: the same bits. */
+VCG_API int vcg_cross_attn_kv_fwd_ex(int dtype, const void* q, long long ldq, const void* kv, long long ldkv, const long long* key_mask, void* ctx, float* stats, int B, int nh, int dh, int Lq, int Lk, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
+/* Its backward. q, kv, key_mask, dropout_p, seed: the forward's arguments; stats [B*nh][Lq][2]: what it wrote; dctx
+   [B*Lq][lddo]: the gradient of ctx (the context itself is not read). Writes dq [B*Lq][lddq] (H columns) and dkv
+   [B*Lk][lddkv] (dK in columns 0..H-1, dV in H..2H-1; every row of every head written once, zeros at a masked key of
+   a sequence that has valid keys); d_ws: B*nh*Lq floats of workspace (D[q] = sum_k P dP from the fp32 products, so
+   that every dS row sums to zero). A sequence without any valid key is uniform over its Lk keys: dS = (1 / Lk)
+   (dP - D) at every key. Rows past B*Lq / B*Lk are never read. Any Lq, Lk >= 1; dh must be 64. bf16: two kernels on
+   mfma_f32_16x16x32_bf16 built from bert_attn_steps.h -- dQ, one workgroup per (sequence, head, 16-query tile), two
+   sweeps (D, then dS and dQ) over the keys in tiles of 128, the four waves' partials combined through LDS in order;
+   dK | dV, one workgroup per (sequence, head, 128-key tile) over all query tiles -- nothing Lq x Lk in HBM (every row
+   pitch a multiple of 8, every pointer 16-B aligned). fp32: one wave per query, then one per key. */
+VCG_API int vcg_cross_attn_kv_bwd(int dtype, const void* q, long long ldq, const void* kv, long long ldkv, const long long* key_mask, const void* dctx, long long lddo, const float* stats, float* d_ws, void* dq, long long lddq, void* dkv, long long lddkv, int B, int nh, int dh, int Lq, int Lk, float scale, float dropout_p, unsigned long long seed, hipStream_t s);
+/* out = dropout(scale * tok[ids] + pos[pos0 + t]), counter row * H + c over out [B*L][H]; dropout_p = 0 is
+   vcg_pegasus_embed_fwd. */
+VCG_API int vcg_pegasus_embed_fwd_ex(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B, int L, int H, int V, int n_pos, float scale, int pos0, float dropout_p, unsigned long long seed, hipStream_t s);
+/* Its backward: tok_grad[id] += scale * dropout'(dout) (fp32, ADDED onto what is there; vcg_gpt_embed_bwd's method and
+   workspace, vcg_ln_bwd_ws_bytes(B*L, H)); rows whose id is pad_idx add nothing; the sinusoidal table is not trained.
+   dtype: dout's, or VCG_BF16 | VCG_GRAD_F32 for an fp32 dout behind a bf16 forward. H <= 1024. */
+VCG_API int vcg_pegasus_embed_bwd(int dtype, const void* dout, const long long* ids, float* tok_grad, float* ws, long long ws_bytes, int B, int L, int H, float scale, long long pad_idx, float dropout_p, unsigned long long seed, hipStream_t s);
+/* LayerNorm backward of an fp32 input WITHOUT a residual (the pre-LayerNorm blocks and final LayerNorms, whose
+   residual stream x [rows][H] is fp32 in every mode; mean, rstd: vcg_ln_fwd's): dh += LN'(dout), dout [rows][H] in
+   `dtype` (the compute dtype, or fp32), dh the fp32 gradient stream, accumulated in one pass; gamma_grad / beta_grad
+   += (either may be NULL). ws: vcg_ln_bwd_ws_bytes(rows, H). H <= 2048. vcg_ln_bwd's classes are untouched. */
+VCG_API int vcg_ln_bwd_acc(int dtype, const void* dout, const float* x, const float* gamma, const float* mean, const float* rstd, float* dh, float* gamma_grad, float* beta_grad, float* ws, long long ws_bytes, int rows, int H, hipStream_t s);
+/* The dropout sites of a pre-LayerNorm block, n = rows * H contiguous elements, counter = element index row * H + c.
+   h, dh: the fp32 residual stream and its gradient; branch, dbranch, pre, f, dy, dpre in `dtype`.
+     vcg_dropout_add_fwd:  h += dropout(branch)          vcg_dropout_add_bwd:  dbranch = dropout'(dh)
+     vcg_relu_dropout_fwd: f = dropout(relu(pre))        vcg_relu_dropout_bwd: dpre = dy * (f > 0 ? 1 / (1 - p) : 0)
+   (a dropped or non-positive element has f = 0: no pre-activation is stored; f may be pre, dpre may be dy). A thread
+   owns 8 elements: 16-byte accesses where every pointer is 16-B aligned, element by element otherwise. */
+VCG_API int vcg_dropout_add_fwd(int dtype, float* h, const void* branch, long long n, float dropout_p, unsigned long long seed, hipStream_t s);
+VCG_API int vcg_dropout_add_bwd(int dtype, const float* dh, void* dbranch, long long n, float dropout_p, unsigned long long seed, hipStream_t s);
+VCG_API int vcg_relu_dropout_fwd(int dtype, const void* pre, void* f, long long n, float dropout_p, unsigned long long seed, hipStream_t s);
+VCG_API int vcg_relu_dropout_bwd(int dtype, const void* dy, const void* f, void* dpre, long long n, float dropout_p, hipStream_t s);
+
 /* ---- gradient exchange over RCCL / xGMI (comm.hip) --------------------------------------------
  * Replaces the NCCL communicator of DDP(model) in train_video_segment_ddp.py:64-86 (init_process_group) and :148
  * (bucketed gradient all-reduce on every backward) and the parameter broadcast of :261-263. One communicator per

@@ -231,6 +231,17 @@ __global__ void gpt_embed_bwd_kernel(const T* __restrict__ dout, float* __restri
   de[idx] = keep(seed, idx, p) ? d / (1.f - p) : 0.f;
 }
 
+// Pegasus: out = dropout(scale * tok[id] + pos[t]) with an untrained position table, so de[row] = scale *
+// dropout'(dout[row]) (counter row * H + c, the forward's) is all embed_scatter_kernel needs
+template <typename T>
+__global__ void pegasus_embed_bwd_kernel(const T* __restrict__ dout, float* __restrict__ de, long long n, float scale,
+                                         float p, uint64_t seed) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const float d = to_f<T>(dout[idx]);
+  de[idx] = keep(seed, idx, p) ? scale * (d / (1.f - p)) : 0.f;
+}
+
 // ---------------------------------------------------------------- residual LayerNorm
 // out = LN(dropout(x) + res)
 template <typename T>
@@ -315,6 +326,56 @@ __global__ void ln_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ 
         if (dres) dres[idx] = from_f<T>(ds);
         if (dx) dx[idx] = from_f<T>(keep(seed, idx, p) ? ds / (1.f - p) : 0.f);
       }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < LN_MAXE; ++e) {
+    const int c = threadIdx.x + e * blockDim.x;
+    if (c < H) {
+      part[(long long)blockIdx.x * 2 * H + c] = pg[e];
+      part[(long long)blockIdx.x * 2 * H + H + c] = pb[e];
+    }
+  }
+}
+
+// y = LN(x) of an fp32 x without a residual and without dropout (the pre-LayerNorm blocks and the final LayerNorms of
+// vcg_hip/pegasus.py, whose residual stream is fp32 in every mode): dh += LN'(dout) in one pass, dout in TD (the compute
+// dtype, or fp32); dgamma / dbeta partial sums per block as ln_bwd_kernel's
+template <typename TD>
+__global__ void ln_bwd_acc_kernel(const TD* __restrict__ dout, const float* __restrict__ x,
+                                  const float* __restrict__ gamma, const float* __restrict__ mean_in,
+                                  const float* __restrict__ rstd_in, float* __restrict__ dh, float* __restrict__ part,
+                                  int H, int rows_per_block, int rows) {
+  __shared__ float red[16];
+  float pg[LN_MAXE], pb[LN_MAXE];
+#pragma unroll
+  for (int e = 0; e < LN_MAXE; ++e) { pg[e] = 0.f; pb[e] = 0.f; }
+  const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+  for (int row = r0; row < r1; ++row) {
+    const float mean = mean_in[row], rstd = rstd_in[row];
+    float xh[LN_MAXE], dxh[LN_MAXE];
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int e = 0; e < LN_MAXE; ++e) {
+      const int c = threadIdx.x + e * blockDim.x;
+      xh[e] = 0.f; dxh[e] = 0.f;
+      if (c < H) {
+        const long long idx = (long long)row * H + c;
+        xh[e] = (x[idx] - mean) * rstd;
+        const float d = to_f<TD>(dout[idx]);
+        pg[e] += d * xh[e];
+        pb[e] += d;
+        dxh[e] = d * gamma[c];
+        a += dxh[e];
+        b += dxh[e] * xh[e];
+      }
+    }
+    a = block_sum(a, red) / H;
+    b = block_sum(b, red) / H;
+#pragma unroll
+    for (int e = 0; e < LN_MAXE; ++e) {
+      const int c = threadIdx.x + e * blockDim.x;
+      if (c < H) dh[(long long)row * H + c] += rstd * (dxh[e] - a - xh[e] * b);
     }
   }
 #pragma unroll
@@ -918,6 +979,37 @@ VCG_API int vcg_gpt_embed_bwd(int dtype, const void* dout, const long long* ids,
   return VCG_OK;
 }
 
+// Pegasus embedding backward: tok_grad[id] += scale * dropout'(dout) by vcg_gpt_embed_bwd's method (fp32 rows, then
+// embed_scatter_kernel: fixed order, no atomics). Rows whose id is pad_idx add nothing (nn.Embedding(padding_idx)).
+// Every id must index tok_grad (the scatter writes row `id`): PegasusHugface.title_loss, the only caller, refuses ids
+// outside [0, vocab_size) on the host before its forward (_check_ids).
+VCG_API int vcg_pegasus_embed_bwd(int dtype, const void* dout, const long long* ids, float* tok_grad, float* ws,
+                                  long long ws_bytes, int B, int L, int H, float scale, long long pad_idx,
+                                  float dropout_p, unsigned long long seed, hipStream_t s) {
+  const int rows = B * L;
+  VCG_REQUIRE(dout && ids && tok_grad && ws && B >= 0 && L >= 0 && H > 0, "invalid arguments");
+  VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
+  if (rows == 0) return VCG_OK;
+  VCG_REQUIRE(ws_bytes >= vcg_ln_bwd_ws_bytes(rows, H), "workspace too small");
+  VCG_REQUIRE(H <= SCAT_MAXE * 256, "hidden size > 1024 not supported by the token-grad reduction");
+  if (dtype & VCG_GRAD_F32) dtype = VCG_F32;  // (only dout is read here)
+  VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
+  int rpb;
+  const int nb = row_blocks(rows, &rpb);
+  float* de = ws + (long long)nb * 2 * H;
+  const long long n = (long long)rows * H;
+  if (dtype == VCG_BF16)
+    hipLaunchKernelGGL(pegasus_embed_bwd_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       (const bf16_t*)dout, de, n, scale, dropout_p, (uint64_t)seed);
+  else
+    hipLaunchKernelGGL(pegasus_embed_bwd_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       (const float*)dout, de, n, scale, dropout_p, (uint64_t)seed);
+  VCG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(embed_scatter_kernel, dim3(rows), dim3(256), 0, s, de, ids, tok_grad, H, (long long)rows, pad_idx);
+  VCG_LAUNCH_CHECK();
+  return VCG_OK;
+}
+
 VCG_API int vcg_ln_fwd(int dtype, const void* x, const void* res, const float* gamma, const float* beta, void* out,
                        float* mean, float* rstd, int rows, int H, float eps, float dropout_p, unsigned long long seed,
                        hipStream_t s) {
@@ -1014,6 +1106,33 @@ VCG_API int vcg_ln_bwd(int dtype, const void* dout, const void* x, const void* r
     VCG_LAUNCH_CHECK();
     hipLaunchKernelGGL(colred_kernel, dim3((H + 63) / 64), dim3(256), 0, s, ws, nb, (long long)H, H, 0LL, bias_grad,
                        (float*)nullptr, 1);
+    VCG_LAUNCH_CHECK();
+  }
+  return VCG_OK;
+}
+
+// LayerNorm backward of an fp32 input without a residual, accumulated onto the fp32 gradient stream: dh += LN'(dout)
+// (dtype: dout's), gamma_grad / beta_grad += (either may be NULL: a frozen LayerNorm).
+VCG_API int vcg_ln_bwd_acc(int dtype, const void* dout, const float* x, const float* gamma, const float* mean,
+                           const float* rstd, float* dh, float* gamma_grad, float* beta_grad, float* ws,
+                           long long ws_bytes, int rows, int H, hipStream_t s) {
+  VCG_REQUIRE(dout && x && gamma && mean && rstd && dh && ws, "null argument");
+  VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
+  VCG_REQUIRE(rows >= 0 && H > 0 && H <= 256 * LN_MAXE, "bad shape (H <= 2048)");
+  if (rows == 0) return VCG_OK;
+  int rpb;
+  const int nb = row_blocks(rows, &rpb);
+  VCG_REQUIRE(ws_bytes >= (long long)nb * 2 * H * 4, "workspace too small");
+  if (dtype == VCG_BF16)
+    hipLaunchKernelGGL(ln_bwd_acc_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)dout, x, gamma, mean, rstd,
+                       dh, ws, H, rpb, rows);
+  else
+    hipLaunchKernelGGL(ln_bwd_acc_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)dout, x, gamma, mean, rstd, dh,
+                       ws, H, rpb, rows);
+  VCG_LAUNCH_CHECK();
+  if (gamma_grad || beta_grad) {
+    hipLaunchKernelGGL(colred_kernel, dim3((H + 63) / 64), dim3(256), 0, s, ws, nb, (long long)2 * H, H, (long long)H,
+                       gamma_grad, beta_grad, 1);
     VCG_LAUNCH_CHECK();
   }
   return VCG_OK;

@@ -55,6 +55,13 @@ __device__ __forceinline__ uint4 ld16(const bf16_t* p, bool ok) {
 }
 
 // ---------------------------------------------------------------------------------------------- coordinates
+// the dropout counter of (head z, query q, key 0) in a score space of Lrows queries per head and row pitch Lp: key
+// k's is + k -- the unfused kernels' element index (self-attention: Head::drop_row; cross-attention: Lrows = Lq,
+// Lp = Lk)
+__device__ __forceinline__ uint64_t drop_row(int z, int Lrows, int q, int Lp) {
+  return ((uint64_t)z * Lrows + q) * (uint64_t)Lp;
+}
+
 // Workgroup blockIdx.x = z * nT + tile of head z = b * nh + h (nT = 1: the L <= 128 kernels). Sequence b is rows
 // row0 .. row0 + L - 1 of qkv / ctx (packed: seq[b] .. seq[b + 1] - 1; else b Lmax .. + Lmax - 1); the stats, the D
 // vector and the dropout counters keep the padded [B * nh][...] index space.
@@ -82,7 +89,7 @@ struct Head {
     so = (long long)z * (nT * LT);
   }
   // the dropout counter of (z, query q, key 0): key k's is + k -- the unfused kernels' element index
-  __device__ __forceinline__ uint64_t drop_row(int q) const { return ((uint64_t)z * Lmax + q) * (uint64_t)Lp; }
+  __device__ __forceinline__ uint64_t drop_row(int q) const { return attn::drop_row(z, Lmax, q, Lp); }
 };
 
 // ---------------------------------------------------------------------------------------------- causal rule

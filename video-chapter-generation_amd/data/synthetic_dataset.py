@@ -73,6 +73,39 @@ class HashGPTTokenizer:
         return _Encoding(ids)
 
 
+class HashPegasusTokenizer:
+    """A deterministic stand-in for transformers.PegasusTokenizer where its sentencepiece file is absent, with the
+    four members the title dataset and PegasusHugface.generate use: `tokenize` splits the text on whitespace
+    (lower-cased), `convert_tokens_to_ids` maps the pad token to 0, the EOS token to 1 (Pegasus' ids) and every other
+    token to 2 + an FNV-1a hash modulo vocab_size - 2, i.e. into [2, vocab_size)."""
+    pad_token, eos_token = "<pad>", "</s>"
+    pad_token_id, eos_token_id = 0, 1
+
+    def __init__(self, vocab_size=96103):
+        if vocab_size < 3:
+            raise ValueError("HashPegasusTokenizer needs a vocabulary of at least 3 ids")
+        self.vocab_size = vocab_size
+
+    def tokenize(self, text):
+        return text.lower().split()
+
+    def _id(self, t):
+        if t == self.pad_token:
+            return 0
+        if t == self.eos_token:
+            return 1
+        h = 0xCBF29CE484222325
+        for b in t.encode():
+            h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+        return 2 + h % (self.vocab_size - 2)
+
+    def convert_tokens_to_ids(self, tokens):
+        return self._id(tokens) if isinstance(tokens, str) else [self._id(t) for t in tokens]
+
+    def decode(self, ids, **kwargs):
+        return " ".join(f"<{int(i)}>" for i in ids)
+
+
 def normalize_frames(u8):
     """u8 [..., H, W, 3] -> f32 [..., 3, H, W] as ToTensor + Normalize (fp32)."""
     x = torch.from_numpy(np.ascontiguousarray(u8)).float() / 255.0

@@ -1,5 +1,5 @@
 """Drop-in for reference model/lang/pegasus_hugface.py:19-146 (PegasusHugface), the chapter-title model of stage 2
-(train_chapter_title_gen.py, test_chapter_title_gen.py, test_whole_pipeline_per_video.py), inference half.
+(train_chapter_title_gen.py, test_chapter_title_gen.py, test_whole_pipeline_per_video.py).
 
 `base_model` is a Pegasus encoder-decoder with transformers' state-dict keys, executed by libvcg_hip
 (vcg_hip/pegasus.py: pre-LayerNorm blocks, fused self- and cross-attention). The reference's
@@ -13,8 +13,9 @@ or $VCG_PEGASUS_CHECKPOINT.
 the encoder and the cross-attention K | V projections once per source and re-run only the decoder per token (the
 reference re-runs the whole model, pegasus_hugface.py:120-122).
 
-Training (a cross-attention backward, a ReLU' epilogue, the tied-embedding and positional backward) is not implemented:
-forward refuses to run where a gradient would be expected.
+Training goes through `title_loss`, which is differentiable (vcg_hip.pegasus.PegasusFn: the engine as one autograd node
+in front of the fused vocabulary loss; dropout in train() mode only). `forward` refuses to run where a gradient would be
+expected: the logits are not differentiated.
 """
 import logging
 import os
@@ -108,9 +109,17 @@ class PegasusHugface(NativeRoot, nn.Module):
     def _check_inference(self):
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError(
-                "PegasusHugface: the native Pegasus is inference-only so far (call .eval() and run under "
-                "torch.no_grad()); training is the follow-up: it needs a cross-attention backward, a ReLU' epilogue "
-                "and the tied-embedding / positional backward")
+                f"PegasusHugface.forward: the logits [B, Ld, {self.vocab_size}] are not differentiated (call .eval() "
+                "and run under torch.no_grad()); training goes through title_loss, which never stores them")
+
+    def _check_ids(self, ids, what):
+        """Token ids index the embedding table in the forward and its gradient in the backward (the scatter kernel
+        writes row `id` of .grad): an id outside [0, vocab_size) -- a tokenizer with another vocabulary -- is refused
+        here, on the host, before anything is launched."""
+        if ids.dtype != torch.int64:
+            raise ValueError(f"title_loss: {what} must be int64 token ids, not {ids.dtype}")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.vocab_size):
+            raise ValueError(f"title_loss: {what} holds a token id outside [0, {self.vocab_size})")
 
     def _engine(self):
         return self.base_model.engine(root=self)
@@ -139,22 +148,47 @@ class PegasusHugface(NativeRoot, nn.Module):
     def title_loss(self, x, attention_mask, decoder_input_ids, decoder_attention_mask, targets):
         """train_chapter_title_gen.py:158-169 / test_chapter_title_gen.py:170-180 without the logits: (mean
         cross-entropy over the decoder positions whose decoder_attention_mask is 1, number of those whose argmax is
-        the target, their number). Only those rows are projected onto the vocabulary (csrc/mlm_head.hip)."""
-        self._check_inference()
+        the target, their number). Only those rows are projected onto the vocabulary (csrc/mlm_head.hip). This is the
+        training entry: with gradients enabled (or in train() mode, where the dropout sites are active) the engine runs
+        as ONE autograd node (vcg_hip.pegasus.PegasusFn) whose output feeds MlmLossFn; loss.backward() adds every
+        trainable parameter's gradient onto its .grad -- with the tied head, the embedding's and the head's onto the
+        same one. In eval mode under torch.no_grad() it is the inference path. No position with mask 1: a NaN loss,
+        nothing launched, every gradient left as it is."""
         from vcg_hip.mlm import MlmLossFn
         dev = x.device
+        self._check_ids(x, "x")
+        if decoder_input_ids is not None:
+            self._check_ids(decoder_input_ids, "decoder_input_ids")
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         keep = decoder_attention_mask.detach().to("cpu").reshape(-1).numpy() != 0
         rows = np.flatnonzero(keep).astype(np.int64)
-        if rows.size == 0:
-            return torch.full((), float("nan"), device=dev), torch.zeros((), dtype=torch.int64, device=dev), 0
+        if rows.size == 0:  # (F.cross_entropy on an empty selection; nothing is launched, no gradient is touched)
+            return (torch.full((), float("nan"), device=dev, requires_grad=grad),
+                    torch.zeros((), dtype=torch.int64, device=dev), 0)
         tgt = targets.detach().to("cpu", torch.int64).reshape(-1).numpy()[rows]
         if ((tgt < 0) | (tgt >= self.vocab_size)).any():
             raise ValueError(f"title_loss: a target outside [0, {self.vocab_size}) at a position with mask 1")
-        hidden = self._decoder_hidden(x, attention_mask, decoder_input_ids, decoder_attention_mask)
-        with torch.no_grad():
-            loss, n_correct = MlmLossFn.apply(hidden, self._anchor(dev), self, self.base_model.lm_head,
-                                              torch.from_numpy(rows).to(dev), torch.from_numpy(tgt.copy()).to(dev),
-                                              None)
+        rows_d, tgt_d = torch.from_numpy(rows).to(dev), torch.from_numpy(tgt.copy()).to(dev)
+        if not self.training and not grad:  # the inference path, as before
+            hidden = self._decoder_hidden(x, attention_mask, decoder_input_ids, decoder_attention_mask)
+            with torch.no_grad():
+                loss, n_correct = MlmLossFn.apply(hidden, self._anchor(dev), self, self.base_model.lm_head, rows_d,
+                                                  tgt_d, None)
+            return loss, n_correct, int(rows.size)
+        from vcg_hip.nn import new_seed
+        from vcg_hip.pegasus import PegasusFn
+        if decoder_input_ids is None:
+            raise ValueError("PegasusHugface.title_loss needs decoder_input_ids")
+        eng = self._engine()
+        seed = new_seed()
+        if grad and any(p.requires_grad for p in self.base_model.model.parameters()):
+            hidden = PegasusFn.apply(self._anchor(dev), eng, x, attention_mask, decoder_input_ids,
+                                     decoder_attention_mask, seed)
+        else:  # only the head trains (fix_backbone), or no gradient at all: nothing is saved, no engine backward
+            with torch.no_grad():
+                hidden, _ = eng.train_forward(x, attention_mask, decoder_input_ids, decoder_attention_mask, seed,
+                                              need_grad=False)
+        loss, n_correct = MlmLossFn.apply(hidden, self._anchor(dev), self, self.base_model.lm_head, rows_d, tgt_d, None)
         return loss, n_correct, int(rows.size)
 
     # ------------------------------------------------------------------ generation

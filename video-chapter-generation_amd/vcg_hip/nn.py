@@ -581,7 +581,8 @@ class PegasusForConditionalGeneration(NativeRoot, nn.Module):
     `embed_positions` (the sinusoidal table: not trained, a checkpoint may overwrite it), `layers.{i}.self_attn.
     {k,v,q,out}_proj`, `self_attn_layer_norm`, `encoder_attn*` (decoder), `fc1`, `fc2`, `final_layer_norm`,
     `layer_norm`, `lm_head` (tied to `shared`) -- executed by vcg_hip/pegasus.py's PegasusEngine: pre-LayerNorm
-    blocks, ReLU, fused self- and cross-attention. Inference only (eval mode).
+    blocks, ReLU, fused self- and cross-attention; inference through encode / cross_kv / decode, training through
+    train_forward / train_backward (model.lang.pegasus_hugface.PegasusHugface.title_loss; dropout in train() mode only).
 
     Not implemented (NotImplementedError): an activation other than relu, a head dim other than 64, a nonzero
     final_logits_bias (pegasus-large's is all zero)."""

@@ -771,20 +771,28 @@ def gpt_embed_bwd(dout, ids, tok_grad, pos_grad, B, L, H, p=0.0, seed=0, storage
               float(p), int(seed) & (2**64 - 1), stream())
 
 
-def pegasus_embed_fwd(ids, tok, pos, B, L, H, dtype, scale, pos0=0):
-    """Pegasus' embedding: scale * tok[ids] + pos[pos0 + t] -> [B*L, H] (fp32 tables, one rounding)."""
+def pegasus_embed_fwd(ids, tok, pos, B, L, H, dtype, scale, pos0=0, p=None, seed=0):
+    """Pegasus' embedding: scale * tok[ids] + pos[pos0 + t] -> [B*L, H] (fp32 tables, one rounding). p (None: the
+    inference entry): dropout on the result, counter row * H + c (dropout_util.row_keep(seed, B * L, H, p))."""
     _chk(ids, torch.int64, "ids")
     _chk(tok, torch.float32, "tok")
     _chk(pos, torch.float32, "pos")
     out = torch.empty((B * L, H), dtype=dtype, device=ids.device)
-    _lib.call("vcg_pegasus_embed_fwd", dt_code(dtype), P(ids), P(tok), P(pos), P(out), B, L, H, tok.shape[0],
-              pos.shape[0], float(scale), int(pos0), stream())
+    if p is None:
+        _lib.call("vcg_pegasus_embed_fwd", dt_code(dtype), P(ids), P(tok), P(pos), P(out), B, L, H, tok.shape[0],
+                  pos.shape[0], float(scale), int(pos0), stream())
+    else:
+        _lib.call("vcg_pegasus_embed_fwd_ex", dt_code(dtype), P(ids), P(tok), P(pos), P(out), B, L, H, tok.shape[0],
+                  pos.shape[0], float(scale), int(pos0), float(p), int(seed) & (2**64 - 1), stream())
     return out
 
 
-def cross_attn_kv_fwd(q, kv, key_mask, B, nh, Lq, Lk, scale, ctx=None, stats=None, dh=64):
+def cross_attn_kv_fwd(q, kv, key_mask, B, nh, Lq, Lk, scale, ctx=None, stats=None, dh=64, dropout_p=None, seed=0):
     """Fused cross-attention forward (csrc/pegasus.hip): q [B*Lq, ldq], kv [B*Lk (+pad), ldkv] = K | V, key_mask int64
-    [B, Lk] or None -> ctx [B*Lq, nh*dh]; stats (optional fp32 [B*nh, Lq, 2]) receives (row max, row sum)."""
+    [B, Lk] or None -> ctx [B*Lq, nh*dh]; stats (optional fp32 [B*nh, Lq, 2]) receives (row max, row sum).
+    dropout_p (None: the inference entry vcg_cross_attn_kv_fwd): the training entry vcg_cross_attn_kv_fwd_ex, P dropped
+    in the score space (z * Lq + q) * Lk + k = dropout_util.score_keep(seed, B * nh, Lq, Lk, p); 0 gives the inference
+    entry's bits."""
     for t, name in ((q, "q"), (kv, "kv")):  # (row-major with any row pitch: column slices of a fused buffer are fine)
         if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype:
             raise RuntimeError(f"{name} must be a 2-D GPU tensor with unit column stride, in q's dtype")
@@ -803,9 +811,128 @@ def cross_attn_kv_fwd(q, kv, key_mask, B, nh, Lq, Lk, scale, ctx=None, stats=Non
         ctx = torch.empty((B * Lq, nh * dh), dtype=q.dtype, device=q.device)
     if stats is not None:
         _chk(stats, torch.float32, "stats")
-    _lib.call("vcg_cross_attn_kv_fwd", dt_code(q.dtype), P(q), q.stride(0), P(kv), kv.stride(0), P(key_mask), P(ctx),
-              P(stats), B, nh, dh, Lq, Lk, float(scale), stream())
+    if dropout_p is None:
+        _lib.call("vcg_cross_attn_kv_fwd", dt_code(q.dtype), P(q), q.stride(0), P(kv), kv.stride(0), P(key_mask),
+                  P(ctx), P(stats), B, nh, dh, Lq, Lk, float(scale), stream())
+    else:
+        _lib.call("vcg_cross_attn_kv_fwd_ex", dt_code(q.dtype), P(q), q.stride(0), P(kv), kv.stride(0), P(key_mask),
+                  P(ctx), P(stats), B, nh, dh, Lq, Lk, float(scale), float(dropout_p), int(seed) & (2**64 - 1),
+                  stream())
     return ctx
+
+
+def cross_attn_kv_bwd(q, kv, key_mask, dctx, stats, B, nh, Lq, Lk, scale, dropout_p=0.0, seed=0, dq=None, dkv=None,
+                      dh=64):
+    """Backward of cross_attn_kv_fwd (two kernels, deterministic): q, kv, key_mask, dropout_p, seed as in the forward,
+    stats [B*nh, Lq, 2] what it wrote, dctx [B*Lq, lddo] the gradient of ctx -> (dq [B*Lq, nh*dh], dkv [B*Lk, 2*nh*dh]
+    = dK | dV); dq / dkv may be given (row-major with any row pitch: column slices are fine)."""
+    H = nh * dh
+    for t, name, rows, cols in ((q, "q", B * Lq, H), (kv, "kv", B * Lk, 2 * H), (dctx, "dctx", B * Lq, H),
+                                (dq, "dq", B * Lq, H), (dkv, "dkv", B * Lk, 2 * H)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype:
+            raise RuntimeError(f"{name} must be a 2-D GPU tensor with unit column stride, in q's dtype")
+        if t.shape[0] < rows or t.shape[1] < cols:
+            raise ValueError(f"cross_attn_kv_bwd: {name} {tuple(t.shape)} too small for B={B} nh={nh} Lq={Lq} Lk={Lk}")
+    _chk(stats, torch.float32, "stats")
+    if stats.numel() < 2 * B * nh * Lq:
+        raise ValueError("cross_attn_kv_bwd: stats smaller than [B*nh, Lq, 2]")
+    if key_mask is not None:
+        _chk(key_mask, torch.int64, "key_mask")
+        if key_mask.numel() < B * Lk:
+            raise ValueError("cross_attn_kv_bwd: key_mask smaller than [B, Lk]")
+    if dq is None:
+        dq = torch.empty((B * Lq, H), dtype=q.dtype, device=q.device)
+    if dkv is None:
+        dkv = torch.empty((B * Lk, 2 * H), dtype=q.dtype, device=q.device)
+    d_ws = torch.empty(B * nh * Lq, dtype=torch.float32, device=q.device)
+    _lib.call("vcg_cross_attn_kv_bwd", dt_code(q.dtype), P(q), q.stride(0), P(kv), kv.stride(0), P(key_mask),
+              P(dctx), dctx.stride(0), P(stats), P(d_ws), P(dq), dq.stride(0), P(dkv), dkv.stride(0), B, nh, dh, Lq, Lk,
+              float(scale), float(dropout_p), int(seed) & (2**64 - 1), stream())
+    return dq, dkv
+
+
+def pegasus_embed_bwd(dout, ids, tok_grad, B, L, H, scale, pad_idx, p=0.0, seed=0, storage_dtype=None):
+    """Backward of pegasus_embed_fwd(..., p, seed): tok_grad[id] += scale * dropout'(dout), fp32, ADDED, fixed order,
+    no atomics; rows whose id is pad_idx add nothing (nn.Embedding(padding_idx)). dout: the forward's dtype, or fp32
+    behind a bf16 forward (storage_dtype=torch.bfloat16: the VCG_GRAD_F32 class)."""
+    _chk(ids, torch.int64, "ids")
+    _chk(tok_grad, torch.float32, "tok_grad")
+    if ids.numel() < B * L or dout.numel() < B * L * H or not dout.is_contiguous():
+        raise ValueError("pegasus_embed_bwd: ids / dout smaller than [B, L] / [B*L, H], or dout not contiguous")
+    if tok_grad.dim() != 2 or tok_grad.shape[1] != H or not tok_grad.is_contiguous():
+        raise ValueError("pegasus_embed_bwd: tok_grad must be a contiguous [V, H]")
+    w = ws(_lib.query("vcg_ln_bwd_ws_bytes", B * L, H), dout.device)
+    code = dt_code(dout.dtype)
+    if storage_dtype is not None and storage_dtype != dout.dtype:
+        if not (storage_dtype == torch.bfloat16 and dout.dtype == torch.float32):
+            raise TypeError(f"pegasus_embed_bwd: dout {dout.dtype} with a {storage_dtype} forward")
+        code = BF16 | GRAD_F32
+    _lib.call("vcg_pegasus_embed_bwd", code, P(dout), P(ids), P(tok_grad), P(w), w.numel() * 4, B, L, H, float(scale),
+              int(pad_idx), float(p), int(seed) & (2**64 - 1), stream())
+
+
+def ln_bwd_acc(dout, x, gamma, mean, rstd, dh, gamma_grad, beta_grad, rows, H):
+    """dh (fp32 gradient stream, in place) += LN'(dout) for y = LN(x) of an fp32 x without a residual (ln_fwd(x, None,
+    ...)'s mean / rstd); dout in the compute dtype or fp32; gamma_grad / beta_grad (fp32, ADDED) may be None."""
+    _chk(x, torch.float32, "x")
+    _chk(dh, torch.float32, "dh")
+    _chk(dout, name="dout")
+    if min(dout.numel(), x.numel(), dh.numel()) < rows * H or mean.numel() < rows or rstd.numel() < rows:
+        raise ValueError(f"ln_bwd_acc: an operand is smaller than [{rows}, {H}]")
+    w = ws(_lib.query("vcg_ln_bwd_ws_bytes", rows, H), dout.device)
+    _lib.call("vcg_ln_bwd_acc", dt_code(dout.dtype), P(dout), P(x), P(gamma), P(mean), P(rstd), P(dh), P(gamma_grad),
+              P(beta_grad), P(w), w.numel() * 4, rows, H, stream())
+    return dh
+
+
+def _ew_check(name, n, *ts):
+    for t in ts:
+        if not t.is_cuda or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"{name}: every operand must be a contiguous GPU tensor of at least {n} elements")
+
+
+def dropout_add_fwd(h, branch, p=0.0, seed=0):
+    """h (fp32 residual stream, in place) += dropout(branch); counter = the element index row * H + c
+    (dropout_util.row_keep)."""
+    _chk(h, torch.float32, "h")
+    n = branch.numel()
+    _ew_check("dropout_add_fwd", n, h, branch)
+    _lib.call("vcg_dropout_add_fwd", dt_code(branch.dtype), P(h), P(branch), n, float(p), int(seed) & (2**64 - 1),
+              stream())
+    return h
+
+
+def dropout_add_bwd(dh, dtype, p=0.0, seed=0):
+    """The branch's gradient dropout'(dh) in `dtype` (dh, fp32, passes through to the stream unchanged)"""
+    _chk(dh, torch.float32, "dh")
+    _ew_check("dropout_add_bwd", dh.numel(), dh)
+    out = torch.empty(dh.shape, dtype=dtype, device=dh.device)
+    _lib.call("vcg_dropout_add_bwd", dt_code(dtype), P(dh), P(out), dh.numel(), float(p), int(seed) & (2**64 - 1),
+              stream())
+    return out
+
+
+def relu_dropout_fwd(pre, p=0.0, seed=0, out=None):
+    """f = dropout(relu(pre)) (out may be pre: in place); counter = the element index"""
+    out = torch.empty_like(pre) if out is None else out
+    if out.dtype != pre.dtype:
+        raise TypeError("relu_dropout_fwd: out must have pre's dtype")
+    _ew_check("relu_dropout_fwd", pre.numel(), pre, out)
+    _lib.call("vcg_relu_dropout_fwd", dt_code(pre.dtype), P(pre), P(out), pre.numel(), float(p),
+              int(seed) & (2**64 - 1), stream())
+    return out
+
+
+def relu_dropout_bwd(dy, f, p=0.0, out=None):
+    """dpre = dy * (f > 0 ? 1 / (1 - p) : 0) from the saved post-dropout activation f (out may be dy: in place)"""
+    out = torch.empty_like(dy) if out is None else out
+    if f.dtype != dy.dtype or out.dtype != dy.dtype:
+        raise TypeError("relu_dropout_bwd: dy, f and out must share a dtype")
+    _ew_check("relu_dropout_bwd", dy.numel(), dy, f, out)
+    _lib.call("vcg_relu_dropout_bwd", dt_code(dy.dtype), P(dy), P(f), P(out), dy.numel(), float(p), stream())
+    return out
 
 
 def attn_softmax_fwd(S, mask, P_out, Pd_out, B, nh, L, Lp, scale, p=0.0, seed=0, causal=False):

@@ -1,7 +1,7 @@
 """BERT attention forward + backward alone, fused (bert_attn.hip / bert_attn_long.hip) vs unfused (QK^T GEMM -> softmax ->
 PV GEMM), B = 64, 12 heads, p = 0.1, L = 128 .. 512 (device events over 20 calls; profiles/long_text_attn_ab.txt). With
 VCG_LIB_PATH it times another build of the library: the fused lines of the parent's and this tree's are compared in
-profiles/bert_attn_shared_ab.txt."""
+profiles/bert_attn_shared_ab.txt and profiles/attn_dkv_shared_ab.txt (--fused-only: only those lines)."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "video-chapter-generation_amd"))
 import torch
@@ -15,7 +15,7 @@ for L in (128, 256, 384, 512):
     dctx = torch.randn(B * L, H).to(torch.bfloat16).cuda()
     n = torch.randint(L // 2, L + 1, (B,))
     mask = (torch.arange(L)[None, :] < n[:, None]).to(torch.int64).cuda()
-    for fused in (True, False):
+    for fused in ((True,) if "--fused-only" in sys.argv[1:] else (True, False)):
         ts = []
         for which in ("fwd", "bwd"):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]

@@ -186,6 +186,8 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--fused-only", action="store_true",
+                    help="only the fused cross-attention arms (A/B of two builds of the library through VCG_LIB_PATH)")
     args = ap.parse_args()
     from vcg_hip import _lib
     _lib.call("vcg_init", 0)
@@ -195,17 +197,25 @@ def main():
           f"maximum] of {args.reps} alternating rounds")
     for name, B in SHAPES.items():
         fns = arms(B, args.iters)
+        if args.fused_only:
+            fns = {k: f for k, f in fns.items() if k[1] == "fused"}
         res = {k: [] for k in fns}
         for rep in range(args.reps):
             order = list(fns) if rep % 2 == 0 else list(fns)[::-1]  # alternating
             for k in order:
                 res[k].append(1e3 * _timed(fns[k], args.runs) / args.iters)
         for ps in ("fwd", "bwd"):
+            if args.fused_only:
+                f = res[(ps, "fused")]
+                print(f"{name:16s} {ps}: fused {statistics.median(f):8.1f} [{min(f):.1f}, {max(f):.1f}]", flush=True)
+                continue
             f, u = res[(ps, "fused")], res[(ps, "unfused")]
             mf, mu = statistics.median(f), statistics.median(u)
             summary[f"{name}_{ps}"] = {"fused_us": mf, "unfused_us": mu}
             print(f"{name:16s} {ps}: fused {mf:8.1f} [{min(f):.1f}, {max(f):.1f}]   unfused {mu:8.1f} "
                   f"[{min(u):.1f}, {max(u):.1f}]   unfused / fused = {mu / mf:.2f}", flush=True)
+    if args.fused_only:
+        return 0
     for name, (fn, nbytes) in streaming(args.iters).items():
         us = [1e3 * _timed(fn, args.runs) / args.iters for _ in range(args.reps)]
         m = statistics.median(us)

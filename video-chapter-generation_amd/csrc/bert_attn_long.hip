@@ -16,7 +16,7 @@
 // The kernels are built from the steps of bert_attn_steps.h, shared with the L <= 128 kernels of bert_attn.hip: the
 // forward and dq hold key-major tiles like that file's forward, dkv query-major tiles like its backward. What is
 // written out here is this algorithm's own: the online softmax, dq's two sweeps with the dropout bits kept in LDS, and
-// the sweeps in halves of 64.
+// the sweeps in halves of 64. dkv's query-tile body (dkv_query_tile) is shared with pegasus.hip's cross-attention.
 //
 // A sequence without any valid key attends uniformly over its L keys (HF's finfo.min bias): a property of the key
 // mask, decided once per workgroup in the forward (every key then counts as valid with score 0) and saved as row
@@ -35,7 +35,7 @@
 //        dPd^T 32 + dQ^T 32 accumulators; 237 VGPRs, no spill. The lane's dropout decisions of sweep 1 are kept as
 //        bits in LDS (each thread rereads its own words) and sweep 2 does not hash again.
 //   dkv: LDS 67.5 KiB (Q, dO row-major 32 + Q^T, dO^T 34 + stats, D 1.5); a tile's queries in two halves of 64, so S 32
-//        + dPd 32 + dV^T, dK^T 64 accumulators; 256 VGPRs, no spill
+//        + dPd 32 + dV^T, dK^T 64 accumulators; 236 VGPRs (causal: 256 and 12 B of scratch), no spill otherwise
 // The tiles are single-buffered (two barriers per tile); at L <= 512 a sweep is at most 4 tiles.
 //
 // CAUSAL instantiations (bert_attn_steps.h, the causal rule): the forward and dq visit key tiles up to their own query
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_fwd_kernel(const bf16_t
     kfirst = kfs;
     none = false;  // (decided per query below)
   } else {
-    int anyk = mask == nullptr;
+    int anyk = mask == nullptr;  // (seq_has_key's rule, kept in this form: see there)
     if (mask)
       for (int k = tid; k < L; k += 256) anyk |= mask[(long long)hd.row0 + k] != 0;
     none = !__syncthreads_or(anyk);
@@ -326,7 +326,9 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dq_kernel(const bf16_t*
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
 // blockIdx.x = z * nT + key tile; wave w owns keys k0 + 32 w .. + 31 (A = Q / dO rows, Q^T / dO^T from LDS, B = the
-// wave's K / V rows from HBM and its Pd / dS fragments from registers).
+// wave's K / V rows from HBM and its Pd / dS fragments from registers). The body of a query tile is
+// dkv_query_tile (bert_attn_steps.h), shared with the cross-attention dK | dV kernel; what is written out here is
+// which query tiles are visited and which of them get the causal body.
 template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t* __restrict__ qkv,
                                                                  const bf16_t* __restrict__ dctx,
@@ -346,7 +348,6 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
   const long long ld = hd.ld;
   if (k0 >= L) return;  // (block-uniform, before any barrier)
   const bf16_t* base = qkv + hd.qo;
-  const bf16_t* dob = dctx + hd.co;
 
   s16x8 kf[2][2], vf[2][2];
   load_frags(kf, base + H, ld, k0 + 32 * w, L, g, i);
@@ -360,68 +361,29 @@ __global__ __launch_bounds__(256, 2) void bert_attn_long_dkv_kernel(const bf16_t
     kv[kt] = key < L && (mask == nullptr || mask[(long long)hd.row0 + key] != 0);
   }
   const bool wact = k0 + 32 * w < L;
-  const float rs = p > 0.f ? 1.f / (1.f - p) : 1.f;
   f32x4 dv[4][2], dk[4][2];  // lane holds dV^T / dK^T [d 16 dt + 4 g + r][key k0 + 32 w + 16 kt + i]
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  const DkvOperands op = {base, dctx + hd.co, ld, H, stats + hd.so, Dv + hd.so, L, L, hd.z, Lmax, Lp,
+                          scale, p, seed};
+  const DkvLds lds = {Qs, dOs, Qt, dOt, st, Ds};
   const bool skip = CAUSAL && causal_skip(mask, hd.row0, L);
-  // one query tile; MASK = the causal rule acts inside it (the diagonal tile, or any tile of a sequence whose first
-  // key is masked; otherwise the non-causal body: every key of the workgroup lies before every query of the tile)
-  auto qtile = [&](auto MASK, int q0) {
-    constexpr bool MK = decltype(MASK)::value;
-    const int Lq = L - q0;
-    const int klo = skip ? k0 + 32 * w - q0 : -NOSKIP;  // the wave's first key in the tile's query coordinates
-    load_transpose(base + (long long)q0 * ld, ld, Lq, Qt, Qs, tid);
-    load_transpose(dob + (long long)q0 * H, H, Lq, dOt, dOs, tid);
-    if (tid < LT) {
-      st[tid] = tid < Lq ? stats[hd.so + q0 + tid] : make_float2(0.f, 0.f);
-      Ds[tid] = tid < Lq ? Dv[hd.so + q0 + tid] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int qh = 0; qh < (wact ? LT : 0) && qh < Lq; qh += 64) {  // the tile's queries in two halves of 64
-      if (MK && qh + 63 < klo) continue;  // (the half lies before the wave's first key)
-      f32x4 sacc[4][2], pacc[4][2];  // lane holds S / dPd [query q0 + qh + 16 qt + 4 g + r][key k0 + 32 w + 16 kt + i]
-      query_tiles<4, MK>(sacc, Qs, qh, Lq, kf, g, i, klo);
-      query_tiles<4, MK>(pacc, dOs, qh, Lq, vf, g, i, klo);
-#pragma unroll
-      for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ql = qh + 16 * qt + 4 * g + r;
-          const float2 mi = st[ql];
-          const float D = Ds[ql];
-          const uint64_t rowi = hd.drop_row(q0 + ql);
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt) {
-            const int key = keyi[kt];
-            const float P = attn_prob(sacc[qt][kt][r], scale, mi, visible<MK>(kv[kt], key, q0 + ql), key < L, ql < Lq);
-            const bool keep = ql < Lq && key < L && dropout_keep(seed, rowi + key, p);
-            const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
-            sacc[qt][kt][r] = keep ? P * rs : 0.f;    // Pd
-            pacc[qt][kt][r] = causal_ds<MK>(scale * P * (dP - D), key, q0 + ql);   // dS
-          }
-        }
-      // dV^T += dO^T Pd, dK^T += Q^T dS (k-step s: queries {32 s + 4 g + r, 32 s + 16 + 4 g + r} of the half)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        if (qh + 32 * s < Lq && (!MK || qh + 32 * s + 31 >= klo))
-          dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], dOt, Qt, qh + 32 * s, g, i);
-    }
-    __syncthreads();
-  };
-  // (causal: the query tiles before the key tile are not visited; the masked body runs on the diagonal tile only,
-  // or on every tile where nothing may be skipped)
+  // (causal: the query tiles before the key tile are not visited; the masked body -- the causal rule acts inside the
+  // tile -- runs on the diagonal tile only, or on every tile of a sequence whose first key is masked, where nothing
+  // may be skipped; the other tiles take the non-causal body: every key of the workgroup lies before every query)
   int q0 = skip ? k0 : 0;
   if constexpr (CAUSAL) {
 #pragma unroll 1
-    for (const int qe = skip ? min(L, k0 + LT) : L; q0 < qe; q0 += LT) qtile(std::true_type{}, q0);
+    for (const int qe = skip ? min(L, k0 + LT) : L; q0 < qe; q0 += LT)  // klo: the wave's first key, tile coordinates
+      dkv_query_tile<true, false>(dv, dk, op, lds, q0, kf, vf, kv, keyi, wact, skip ? k0 + 32 * w - q0 : -NOSKIP, tid,
+                                  g, i);
   }
 #pragma unroll 1
-  for (; q0 < L; q0 += LT) qtile(std::false_type{}, q0);
+  for (; q0 < L; q0 += LT)
+    dkv_query_tile<false, false>(dv, dk, op, lds, q0, kf, vf, kv, keyi, wact, -NOSKIP, tid, g, i);
   if (!wact) return;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {

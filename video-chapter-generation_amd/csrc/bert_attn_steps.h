@@ -1,9 +1,11 @@
-// The fused BERT attention kernels' tile constants, MFMA fragment helpers and the steps all five kernels are built from,
-// each written once (bert_attn.hip: L <= 128, one workgroup per (sequence, head); bert_attn_long.hip: 128 < L <= 512,
-// 128 x 128 tiles with an online softmax). What the packed and the padded paths, the forwards and the backwards must
-// agree on bit for bit -- the masking rule and the no-key convention (attn_prob), the dropout counter (Head::drop_row,
-// dropout_frags) -- is stated here and nowhere else. Every step is __forceinline__ and takes the lane decomposition
-// (g, i) and the tile-skip bounds as arguments; a 256-thread workgroup of 4 waves is assumed throughout.
+// The fused attention kernels' tile constants, MFMA fragment helpers and the steps the kernels are built from, each
+// written once: the five self-attention kernels (bert_attn.hip: L <= 128, one workgroup per (sequence, head);
+// bert_attn_long.hip: 128 < L <= 512, 128 x 128 tiles with an online softmax) and the three bf16 cross-attention
+// kernels of pegasus.hip (Lq != Lk, separate Q and K | V buffers). What the packed and the padded paths, the forwards
+// and the backwards, self- and cross-attention must agree on bit for bit -- the masking rule and the no-key convention
+// (attn_prob, seq_has_key), the dropout counter (drop_row, dropout_frags), the dK | dV rule of a query tile
+// (dkv_query_tile) -- is stated here and nowhere else. Every step is __forceinline__ and takes the lane
+// decomposition (g, i) and the tile-skip bounds as arguments; a 256-thread workgroup of 4 waves is assumed throughout.
 //
 // MFMA: mfma_f32_16x16x32_bf16 (lane l = 16 g + i holds A[row i][k-set g], B[k-set g][col i], D[rows 4g..4g+3]
 // [col i]). A k-step's 32 k indices only have to be the same SET on both operands, so a D fragment (4 consecutive
@@ -106,6 +108,17 @@ constexpr int NOSKIP = 1 << 20;  // a first-query / first-key bound under which 
 // may tiles wholly above the diagonal be skipped? (not when some query has no visible key: see above)
 __device__ __forceinline__ bool causal_skip(const long long* mask, long long row0, int L) {
   return mask == nullptr || L <= 0 || mask[row0] != 0;
+}
+// do rows row .. row + L - 1 of the mask, one sequence's keys, hold any valid key? (mask NULL: yes.) Block-uniform;
+// every thread must call it (a barrier). Without one the sequence attends uniformly: attn_prob's no-key convention.
+// (The cross-attention forwards' scan. bert_attn_long_fwd_kernel keeps its own lines, which differ in the stride -- the
+// constant 256 -- and in reaching the barrier with a NULL mask too: through this function its L >= 384 timings moved
+// by 0.5 %, profiles/attn_dkv_shared_ab.txt.)
+__device__ __forceinline__ bool seq_has_key(const long long* mask, long long row, int L) {
+  if (mask == nullptr) return true;
+  int any = 0;
+  for (int k = threadIdx.x; k < L; k += blockDim.x) any |= mask[row + k] != 0;
+  return __syncthreads_or(any) != 0;
 }
 
 // the causal cut of dS: no gradient reaches a future key's score -- HF's `w * b + -1e4 (1 - b)` fill multiplies it by
@@ -301,6 +314,82 @@ __device__ __forceinline__ void dvdk_step(f32x4 (&dv)[4][2], f32x4 (&dk)[4][2], 
       dk[dt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, sb[kt], dk[dt][kt], 0, 0, 0);
     }
   }
+}
+
+// One 128-query tile of a dK | dV workgroup (bert_attn_long_dkv_kernel, pegasus.hip's cross_attn_kv_dkv_kernel): the
+// workgroup owns a key tile, wave w its keys k0 + 32 w .. + 31 (K / V fragments kf / vf, validity kv, indices keyi),
+// and adds this query tile's share to dv / dk. The operands are one head's: query q is row q of Q / dO / stats / D.
+struct DkvOperands {
+  const bf16_t *q, *dO;   // row 0 of the head's Q and dO
+  long long ldq, lddo;    // their row pitches
+  const float2* stats;    // the saved row statistics (SUM: (max, sum), cross-attention; else (max, 1 / sum))
+  const float* D;         // the dq kernel's D = rowsum(P o dP)
+  int nq, nk;             // queries and keys of the sequence
+  int z, Lrows, Lp;       // the dropout counter's space (drop_row)
+  float scale, p;         // score scale, dropout p
+  uint64_t seed;
+};
+struct DkvLds {
+  bf16_t *Qs, *dOs;  // [LT][64] swizzled row-major
+  bf16_t *Qt, *dOt;  // [64][TP] transposed
+  float2* st;        // [LT], attn_prob's form
+  float* Ds;         // [LT]
+};
+// Stages the tile (queries q0 .. q0 + 127, rows past nq zero), then sweeps it in two halves of 64: S = Q K^T and
+// dPd = dO V^T (query_tiles), P from the statistics, Pd = keep P / (1 - p), dS = scale P o (keep dPd / (1 - p) - D),
+// dV^T += dO^T Pd and dK^T += Q^T dS (dvdk_step). Two barriers; every thread of the workgroup must call it, a wave
+// past the keys' end (!wact) only loads and syncs. MK: the causal rule acts inside this tile -- klo is the wave's
+// first key in the tile's query coordinates (-NOSKIP: nothing skipped), and the halves, 16 x 16 tiles and k-steps
+// wholly above the diagonal are skipped; !MK is the non-causal body (every key visible to every query, klo unused).
+template <bool MK, bool SUM>
+__device__ __forceinline__ void dkv_query_tile(f32x4 (&dv)[4][2], f32x4 (&dk)[4][2], const DkvOperands& op,
+                                               const DkvLds& lds, int q0, const s16x8 (&kf)[2][2],
+                                               const s16x8 (&vf)[2][2], const bool (&kv)[2], const int (&keyi)[2],
+                                               bool wact, int klo, int tid, int g, int i) {
+  const int Lq = op.nq - q0;  // queries from this tile on (>= 128: a full tile)
+  const float rs = op.p > 0.f ? 1.f / (1.f - op.p) : 1.f;
+  load_transpose(op.q + (long long)q0 * op.ldq, op.ldq, Lq, lds.Qt, lds.Qs, tid);
+  load_transpose(op.dO + (long long)q0 * op.lddo, op.lddo, Lq, lds.dOt, lds.dOs, tid);
+  if (tid < LT) {
+    float2 m = tid < Lq ? op.stats[q0 + tid] : make_float2(0.f, 0.f);
+    if (SUM && tid < Lq) m.y = 1.f / m.y;  // attn_prob's form
+    lds.st[tid] = m;
+    lds.Ds[tid] = tid < Lq ? op.D[q0 + tid] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int qh = 0; qh < (wact ? LT : 0) && qh < Lq; qh += 64) {  // the tile's queries in two halves of 64
+    if (MK && qh + 63 < klo) continue;  // (the half lies before the wave's first key)
+    f32x4 sacc[4][2], pacc[4][2];  // lane holds S / dPd [query q0 + qh + 16 qt + 4 g + r][key k0 + 32 w + 16 kt + i]
+    query_tiles<4, MK>(sacc, lds.Qs, qh, Lq, kf, g, i, klo);
+    query_tiles<4, MK>(pacc, lds.dOs, qh, Lq, vf, g, i, klo);
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ql = qh + 16 * qt + 4 * g + r;
+        const float2 mi = lds.st[ql];
+        const float D = lds.Ds[ql];
+        const uint64_t rowi = drop_row(op.z, op.Lrows, q0 + ql, op.Lp);
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+          const int key = keyi[kt];
+          const float P = attn_prob(sacc[qt][kt][r], op.scale, mi, visible<MK>(kv[kt], key, q0 + ql), key < op.nk,
+                                    ql < Lq);
+          const bool keep = ql < Lq && key < op.nk && dropout_keep(op.seed, rowi + key, op.p);
+          const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
+          sacc[qt][kt][r] = keep ? P * rs : 0.f;                                     // Pd
+          pacc[qt][kt][r] = causal_ds<MK>(op.scale * P * (dP - D), key, q0 + ql);  // dS
+        }
+      }
+    // dV^T += dO^T Pd, dK^T += Q^T dS (k-step s: queries {32 s + 4 g + r, 32 s + 16 + 4 g + r} of the half)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      if (qh + 32 * s < Lq && (!MK || qh + 32 * s + 31 >= klo))
+        dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], lds.dOt, lds.Qt, qh + 32 * s, g,
+                  i);
+  }
+  __syncthreads();  // every wave is done with this tile before the next one overwrites it
 }
 
 // ---------------------------------------------------------------------------------------------- store

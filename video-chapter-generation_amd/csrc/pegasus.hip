@@ -16,13 +16,41 @@ namespace {
 
 constexpr int QT = 16;  // queries of a workgroup: one MFMA tile
 
-// does sequence row `row` .. + Lk - 1 of the mask hold any valid key? (block-uniform; every thread must call it)
-__device__ __forceinline__ bool seq_has_key(const long long* mask, long long row, int Lk) {
-  if (mask == nullptr) return true;
-  int any = 0;
-  for (int k = threadIdx.x; k < Lk; k += blockDim.x) any |= mask[row + k] != 0;
-  return __syncthreads_or(any) != 0;
-}
+// The bf16 cross-attention kernels' coordinates (attn::Head's counterpart). Workgroup blockIdx.x = z * nT + tile of
+// head z = b * nh + h, nT tiles per head (of 16 queries, or of 128 keys). Sequence b is rows b Lq .. of q / dctx / dq /
+// ctx and rows b Lk .. of kv / dkv / the mask; the stats, D and the dropout counters are indexed [z][Lq]. (The fp32
+// parity kernels, one wave per query or key row, keep their own few lines: they index single rows. The lane
+// decomposition stays one line in each kernel.)
+struct CrossHead {
+  int z, h, H, Lq;       // H = nh * 64
+  unsigned tile;         // (unsigned like blockIdx.x; the workgroup's first row is QT * tile or LT * tile)
+  long long qrow, mrow;  // the first query row and the first key (mask) row of sequence b
+  const bf16_t *Q, *K, *V;  // row 0 of (b, h) in q and in kv (V at K + H)
+
+  __device__ __forceinline__ CrossHead(const bf16_t* q, long long ldq, const bf16_t* kv, long long ldkv, int nh, int Lq_,
+                                       int Lk, int nT) : Lq(Lq_) {
+    z = blockIdx.x / nT;
+    tile = blockIdx.x - z * nT;
+    const int b = z / nh;
+    h = z - b * nh;
+    H = nh * DH;
+    qrow = (long long)b * Lq;
+    mrow = (long long)b * Lk;
+    Q = qrows(q, ldq);
+    K = krows(kv, ldkv);
+    V = K + H;
+  }
+  // the stats / D row of (z, query 0). Like the two below it is formed where it is used, not in the constructor: the
+  // kernels then compile to what they were with these lines written out
+  __device__ __forceinline__ long long srow() const { return (long long)z * Lq; }
+  // (b, h)'s row r0 + r1 of a query-indexed buffer (q, dctx, dq, ctx) / row r of a key-indexed one (kv, dkv), pitch ld
+  template <typename U>
+  __device__ __forceinline__ U* qrows(U* p, long long ld, int r0 = 0, int r1 = 0) const {
+    return p + (qrow + r0 + r1) * ld + h * DH;
+  }
+  template <typename U>
+  __device__ __forceinline__ U* krows(U* p, long long ld, int r = 0) const { return p + (mrow + r) * ld + h * DH; }
+};
 
 // One workgroup (4 waves) per (sequence b, head h, 16-query tile). The keys go by in tiles of LT = 128: the workgroup
 // transposes the tile's V into LDS (load_transpose: the A operand of O^T += V^T P^T), wave w owns the tile's keys
@@ -47,14 +75,10 @@ __global__ __launch_bounds__(256) void cross_attn_kv_fwd_kernel(const bf16_t* __
   __shared__ float sm[4][QT], sl[4][QT];
   __shared__ __attribute__((aligned(16))) float so[4][QT][DH];
 
-  const int z = blockIdx.x / nQ, q0 = QT * (blockIdx.x - z * nQ);
-  const int b = z / nh, h = z - b * nh;
-  const int H = nh * DH;
-  const int tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
-  const bf16_t* Qs = q + (long long)b * Lq * ldq + h * DH;
-  const bf16_t* Ks = kv + (long long)b * Lk * ldkv + h * DH;
-  const bf16_t* Vs = Ks + H;
-  const long long mrow = (long long)b * Lk;
+  const CrossHead hd(q, ldq, kv, ldkv, nh, Lq, Lk, nQ);
+  const int z = hd.z, q0 = QT * hd.tile, H = hd.H, tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
+  const bf16_t *Qs = hd.Q, *Ks = hd.K, *Vs = hd.V;
+  const long long mrow = hd.mrow;
   const bool has_key = seq_has_key(mask, mrow, Lk);
   const bool qrow = q0 + i < Lq;
 
@@ -148,9 +172,9 @@ __global__ __launch_bounds__(256) void cross_attn_kv_fwd_kernel(const bf16_t* __
     o += *reinterpret_cast<const f32x4*>(&so[ww][qi][d0]) * f;
   }
   const float inv = 1.f / lt;
-  *reinterpret_cast<uint2*>(ctx + ((long long)b * Lq + q0 + qi) * H + h * DH + d0) =
+  *reinterpret_cast<uint2*>(hd.qrows(ctx, H, q0, qi) + d0) =
       make_uint2(pack2(o[0] * inv, o[1] * inv), pack2(o[2] * inv, o[3] * inv));
-  if (stats && d0 == 0) stats[(long long)z * Lq + q0 + qi] = make_float2(has_key ? mt : -INFINITY, lt);
+  if (stats && d0 == 0) stats[hd.srow() + q0 + qi] = make_float2(has_key ? mt : -INFINITY, lt);
 }
 
 // The fp32 parity mode: one wave per (sequence, head, query). Lane j owns keys j, j + 64, ... with an online softmax
@@ -212,19 +236,23 @@ __global__ __launch_bounds__(64) void cross_attn_kv_fwd_f32_kernel(const float* 
 }
 
 // out[b, t] = scale * tok[ids[b, t]] + pos[pos0 + t]: the product and the sum in double (exact up to its own
-// rounding), one rounding to fp32, and from there to the storage dtype
-template <typename T>
+// rounding), one rounding to fp32, and from there to the storage dtype. DROP (training): dropout of that fp32 value,
+// counter row * H + c (the element index of out), 1 / (1 - p) in fp32
+template <typename T, bool DROP>
 __global__ void pegasus_embed_fwd_kernel(const long long* __restrict__ ids, const float* __restrict__ tok,
                                          const float* __restrict__ pos, T* __restrict__ out, int L, int H, int V,
-                                         float scale, int pos0) {
+                                         float scale, int pos0, float pdrop, uint64_t seed) {
   const long long row = blockIdx.x;
   const int t = (int)(row % L);
   long long id = ids[row];
   id = id < 0 ? 0 : (id >= V ? V - 1 : id);  // (ids are validated where they are made; never read outside the table)
   const float* tr = tok + id * H;
   const float* pr = pos + (long long)(pos0 + t) * H;
-  for (int c = threadIdx.x; c < H; c += blockDim.x)
-    out[row * H + c] = from_f<T>((float)((double)scale * (double)tr[c] + (double)pr[c]));
+  for (int c = threadIdx.x; c < H; c += blockDim.x) {
+    float v = (float)((double)scale * (double)tr[c] + (double)pr[c]);
+    if constexpr (DROP) v = dropout_keep(seed, (uint64_t)(row * H + c), pdrop) ? v / (1.f - pdrop) : 0.f;
+    out[row * H + c] = from_f<T>(v);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ training
@@ -255,20 +283,15 @@ __global__ __launch_bounds__(256) void cross_attn_kv_dq_kernel(const bf16_t* __r
   __shared__ float sD[4][QT];
   __shared__ __attribute__((aligned(16))) float so[4][QT][DH];
 
-  const int z = blockIdx.x / nQ, q0 = QT * (blockIdx.x - z * nQ);
-  const int b = z / nh, h = z - b * nh;
-  const int H = nh * DH;
-  const int tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
-  const bf16_t* Qs = q + (long long)b * Lq * ldq + h * DH;
-  const bf16_t* dOs = dctx + (long long)b * Lq * lddo + h * DH;
-  const bf16_t* Ks = kv + (long long)b * Lk * ldkv + h * DH;
-  const bf16_t* Vs = Ks + H;
-  const long long mrow = (long long)b * Lk;
+  const CrossHead hd(q, ldq, kv, ldkv, nh, Lq, Lk, nQ);
+  const int z = hd.z, q0 = QT * hd.tile, tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
+  const bf16_t *Qs = hd.Q, *dOs = hd.qrows(dctx, lddo), *Ks = hd.K, *Vs = hd.V;
+  const long long mrow = hd.mrow;
   const bool qrow = q0 + i < Lq;
 
   float2 mi = make_float2(0.f, 0.f);  // (row max, 1 / row sum): attn_prob's form
   if (qrow) {
-    mi = stats[(long long)z * Lq + q0 + i];
+    mi = stats[hd.srow() + q0 + i];
     mi.y = 1.f / mi.y;
   }
   const float rs = pdrop > 0.f ? 1.f / (1.f - pdrop) : 1.f;
@@ -334,7 +357,7 @@ __global__ __launch_bounds__(256) void cross_attn_kv_dq_kernel(const bf16_t* __r
       if (g == 0) sD[w][i] = D;
       __syncthreads();
       D = ((sD[0][i] + sD[1][i]) + sD[2][i]) + sD[3][i];
-      if (w == 0 && g == 0 && qrow) Dv[(long long)z * Lq + q0 + i] = D;
+      if (w == 0 && g == 0 && qrow) Dv[hd.srow() + q0 + i] = D;
     }
   }
   // the wave's partial dQ^T[d = 16 dt + 4 g + r][query i]; thread (query qi, 4 dims from d0) adds the four in order
@@ -346,15 +369,14 @@ __global__ __launch_bounds__(256) void cross_attn_kv_dq_kernel(const bf16_t* __r
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ww = 0; ww < 4; ++ww) o += *reinterpret_cast<const f32x4*>(&so[ww][qi][d0]);
-  *reinterpret_cast<uint2*>(dq + ((long long)b * Lq + q0 + qi) * lddq + h * DH + d0) =
+  *reinterpret_cast<uint2*>(hd.qrows(dq, lddq, q0, qi) + d0) =
       make_uint2(pack2(o[0], o[1]), pack2(o[2], o[3]));
 }
 
 // dK | dV: one workgroup per (sequence b, head h, 128-key tile); wave w owns keys k0 + 32 w .. + 31 and keeps their K
-// and V fragments and the dV^T / dK^T accumulators in registers. It sweeps ALL query tiles in the query-major form of
-// the self-attention dkv kernel (query_tiles for S = Q K^T and dPd = dO V^T with A = Q / dO rows from LDS, dvdk_step
-// for dV^T += dO^T Pd and dK^T += Q^T dS), in halves of 64 queries, with the saved statistics and the first kernel's D.
-// Every key's dK and dV row is written exactly once.
+// and V fragments and the dV^T / dK^T accumulators in registers. It sweeps ALL query tiles with the self-attention dkv
+// kernel's tile body, dkv_query_tile (bert_attn_steps.h: the non-causal instantiation, statistics saved as (max,
+// sum)), with the first kernel's D. Every key's dK and dV row is written exactly once.
 __global__ __launch_bounds__(256, 2) void cross_attn_kv_dkv_kernel(const bf16_t* __restrict__ q, long long ldq,
                                                                    const bf16_t* __restrict__ kv, long long ldkv,
                                                                    const long long* __restrict__ mask,
@@ -369,86 +391,39 @@ __global__ __launch_bounds__(256, 2) void cross_attn_kv_dkv_kernel(const bf16_t*
   __shared__ __attribute__((aligned(16))) bf16_t dOt[DH * TP];
   __shared__ float2 st[LT];
   __shared__ float Ds[LT];
-  const int z = blockIdx.x / nK, k0 = LT * (blockIdx.x - z * nK);
-  const int b = z / nh, h = z - b * nh;
-  const int H = nh * DH;
-  const int tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
-  const bf16_t* Qs = q + (long long)b * Lq * ldq + h * DH;
-  const bf16_t* dOs = dctx + (long long)b * Lq * lddo + h * DH;
-  const bf16_t* Ks = kv + (long long)b * Lk * ldkv + h * DH;
-  const long long mrow = (long long)b * Lk, srow = (long long)z * Lq;
+  const CrossHead hd(q, ldq, kv, ldkv, nh, Lq, Lk, nK);
+  const int k0 = LT * hd.tile, H = hd.H, tid = threadIdx.x, w = tid >> 6, g = (tid & 63) >> 4, i = tid & 15;
 
   s16x8 kf[2][2], vf[2][2];
-  load_frags(kf, Ks, ldkv, k0 + 32 * w, Lk, g, i);
-  load_frags(vf, Ks + H, ldkv, k0 + 32 * w, Lk, g, i);
+  load_frags(kf, hd.K, ldkv, k0 + 32 * w, Lk, g, i);
+  load_frags(vf, hd.V, ldkv, k0 + 32 * w, Lk, g, i);
   bool kvalid[2];
   int keyi[2];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     const int key = k0 + 32 * w + 16 * kt + i;
     keyi[kt] = key;
-    kvalid[kt] = key < Lk && (mask == nullptr || mask[mrow + key] != 0);
+    kvalid[kt] = key < Lk && (mask == nullptr || mask[hd.mrow + key] != 0);
   }
   const bool wact = k0 + 32 * w < Lk;  // (else the wave only loads and syncs)
-  const float rs = pdrop > 0.f ? 1.f / (1.f - pdrop) : 1.f;
   f32x4 dv[4][2], dk[4][2];  // lane holds dV^T / dK^T [d 16 dt + 4 g + r][key k0 + 32 w + 16 kt + i]
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) dv[dt][kt] = dk[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  const DkvOperands op = {hd.Q, hd.qrows(dctx, lddo), ldq, lddo, stats + hd.srow(), Dv + hd.srow(), Lq, Lk, hd.z, Lq, Lk,
+                          scale, pdrop, seed};
+  const DkvLds lds = {Qr, dOr, Qt, dOt, st, Ds};
 #pragma unroll 1
-  for (int q0 = 0; q0 < Lq; q0 += LT) {
-    const int Lr = Lq - q0;  // queries from this tile on (>= 128: a full tile)
-    load_transpose(Qs + (long long)q0 * ldq, ldq, Lr, Qt, Qr, tid);
-    load_transpose(dOs + (long long)q0 * lddo, lddo, Lr, dOt, dOr, tid);
-    if (tid < LT) {
-      float2 m = make_float2(0.f, 0.f);
-      if (tid < Lr) {
-        m = stats[srow + q0 + tid];
-        m.y = 1.f / m.y;  // attn_prob's form
-      }
-      st[tid] = m;
-      Ds[tid] = tid < Lr ? Dv[srow + q0 + tid] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int qh = 0; qh < (wact ? LT : 0) && qh < Lr; qh += 64) {  // the tile's queries in two halves of 64
-      f32x4 sacc[4][2], pacc[4][2];  // lane holds S / dPd [query q0 + qh + 16 qt + 4 g + r][key k0 + 32 w + 16 kt + i]
-      query_tiles<4>(sacc, Qr, qh, Lr, kf, g, i);
-      query_tiles<4>(pacc, dOr, qh, Lr, vf, g, i);
-#pragma unroll
-      for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ql = qh + 16 * qt + 4 * g + r;
-          const float2 mi = st[ql];
-          const float D = Ds[ql];
-          const uint64_t rowi = drop_row(z, Lq, q0 + ql, Lk);
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt) {
-            const int key = keyi[kt];
-            const float P = attn_prob(sacc[qt][kt][r], scale, mi, kvalid[kt], key < Lk, ql < Lr);
-            const bool keep = ql < Lr && key < Lk && dropout_keep(seed, rowi + key, pdrop);
-            const float dP = keep ? pacc[qt][kt][r] * rs : 0.f;
-            sacc[qt][kt][r] = keep ? P * rs : 0.f;        // Pd
-            pacc[qt][kt][r] = scale * P * (dP - D);       // dS
-          }
-        }
-      // dV^T += dO^T Pd, dK^T += Q^T dS (k-step s: queries {32 s + 4 g + r, 32 s + 16 + 4 g + r} of the half)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-        if (qh + 32 * s < Lr)
-          dvdk_step(dv, dk, sacc[2 * s], sacc[2 * s + 1], pacc[2 * s], pacc[2 * s + 1], dOt, Qt, qh + 32 * s, g, i);
-    }
-    __syncthreads();  // every wave is done with this tile before the next one overwrites it
-  }
+  for (int q0 = 0; q0 < Lq; q0 += LT)
+    dkv_query_tile<false, true>(dv, dk, op, lds, q0, kf, vf, kvalid, keyi, wact, -NOSKIP, tid, g, i);
   if (!wact) return;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     const int key = keyi[kt];
     if (key < Lk) {
-      bf16_t* o = dkv + (mrow + key) * lddkv + h * DH + 4 * g;
+      bf16_t* o = hd.krows(dkv, lddkv, key) + 4 * g;
       store_row64(o, dk, kt);
       store_row64(o + H, dv, kt);
     }
@@ -588,24 +563,6 @@ __global__ __launch_bounds__(64) void cross_attn_kv_dkv_f32_kernel(const float* 
   out[H + lane] = o;
 }
 
-// out[row] = dropout(scale * tok[ids[row]] + pos[pos0 + t]), counter row * H + c (the element index of out); the
-// undropped value is pegasus_embed_fwd_kernel's (double, one rounding to fp32), then 1 / (1 - p) in fp32
-template <typename T>
-__global__ void pegasus_embed_drop_fwd_kernel(const long long* __restrict__ ids, const float* __restrict__ tok,
-                                              const float* __restrict__ pos, T* __restrict__ out, int L, int H, int V,
-                                              float scale, int pos0, float pdrop, uint64_t seed) {
-  const long long row = blockIdx.x;
-  const int t = (int)(row % L);
-  long long id = ids[row];
-  id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-  const float* tr = tok + id * H;
-  const float* pr = pos + (long long)(pos0 + t) * H;
-  for (int c = threadIdx.x; c < H; c += blockDim.x) {
-    const float v = (float)((double)scale * (double)tr[c] + (double)pr[c]);
-    out[row * H + c] = from_f<T>(dropout_keep(seed, (uint64_t)(row * H + c), pdrop) ? v / (1.f - pdrop) : 0.f);
-  }
-}
-
 // The pre-LayerNorm blocks' dropout sites as streaming kernels over n = rows * H elements, counter = the element index
 // row * H + c. h is the fp32 residual stream, T the compute dtype. A thread owns 8 consecutive elements: 16-byte
 // accesses (one per bf16 operand, two per fp32 operand) where `vec` says every pointer is 16-B aligned, element by
@@ -711,23 +668,50 @@ __global__ void relu_dropout_bwd_kernel(const T* dy, const T* f, T* dpre, long l
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// The checks the cross-attention entries share (bert_attn.hip's attn_check): head dim, the null test the caller made,
+// dtype, shape, dropout_p, every buffer's row pitch against its least (H for a query-indexed one, 2 H for K | V) and,
+// in bf16, the 16-B alignment of every buffer and pitch, in the entries' order: the grid test the caller made
+// (grid_ok) comes before the alignment. fn: the entry's name; pitch_msg: its text for a short pitch; ctx_aligned: an
+// output without a pitch argument.
+struct CrossBuf {
+  const void* p;
+  long long ld;
+  int nH;  // the pitch is at least nH * H
+};
+int cross_check(const char* fn, bool nonnull, int dtype, int B, int nh, int dh, int Lq, int Lk, float dropout_p,
+                std::initializer_list<CrossBuf> bufs, const char* pitch_msg, bool grid_ok, bool ctx_aligned = true) {
+  const char* msg = nullptr;
+  bool pitch = true, align = ctx_aligned;
+  for (const CrossBuf& b : bufs) {
+    pitch = pitch && b.ld >= (long long)b.nH * nh * DH;
+    align = align && b.ld % 8 == 0 && aligned16(b.p);
+  }
+  if (dh != DH) msg = "head dim must be 64";
+  else if (!nonnull) msg = "null argument";
+  else if (dtype != VCG_F32 && dtype != VCG_BF16) msg = "dtype must be VCG_F32 or VCG_BF16";
+  else if (!(B > 0 && nh > 0 && Lq >= 1 && Lk >= 1)) msg = "bad shape";
+  else if (!(dropout_p >= 0.f && dropout_p < 1.f)) msg = "dropout_p must be in [0, 1)";
+  else if (!pitch) msg = pitch_msg;
+  else if (!grid_ok) msg = "grid too large";
+  else if (dtype == VCG_BF16 && !align) msg = "16-B alignment";
+  if (msg == nullptr) return VCG_OK;
+  set_error(std::string(fn) + ": " + msg);
+  return VCG_ERR_INVALID;
+}
+
 }  // namespace
 
 VCG_API int vcg_cross_attn_kv_fwd_ex(int dtype, const void* q, long long ldq, const void* kv, long long ldkv,
                                      const long long* key_mask, void* ctx, float* stats, int B, int nh, int dh, int Lq,
                                      int Lk, float scale, float dropout_p, unsigned long long seed, hipStream_t s) {
-  VCG_REQUIRE(dh == DH, "head dim must be 64");
-  VCG_REQUIRE(q && kv && ctx, "null argument");
-  VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
-  VCG_REQUIRE(B > 0 && nh > 0 && Lq >= 1 && Lk >= 1, "bad shape");
-  VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
-  const long long H = (long long)nh * DH;
-  VCG_REQUIRE(ldq >= H && ldkv >= 2 * H, "ldq < H or ldkv < 2 H");
-  VCG_REQUIRE((long long)B * nh * ((Lq + QT - 1) / QT) < (1LL << 31) && (long long)B * nh * Lq < (1LL << 31),
-              "grid too large");
+  const int rc = cross_check(__func__, q && kv && ctx, dtype, B, nh, dh, Lq, Lk, dropout_p,
+                             {{q, ldq, 1}, {kv, ldkv, 2}}, "ldq < H or ldkv < 2 H",
+                             (long long)B * nh * ((Lq + QT - 1) / QT) < (1LL << 31) &&
+                                 (long long)B * nh * Lq < (1LL << 31),
+                             aligned16(ctx));
+  if (rc != VCG_OK) return rc;
   const bool drop = dropout_p > 0.f;  // (p = 0: the inference kernels, bit for bit)
   if (dtype == VCG_BF16) {
-    VCG_REQUIRE(ldq % 8 == 0 && ldkv % 8 == 0 && aligned16(q) && aligned16(kv) && aligned16(ctx), "16-B alignment");
     const int nQ = (Lq + QT - 1) / QT;
     hipLaunchKernelGGL(drop ? cross_attn_kv_fwd_kernel<true> : cross_attn_kv_fwd_kernel<false>, dim3(B * nh * nQ),
                        dim3(256), 0, s, (const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, key_mask, (bf16_t*)ctx,
@@ -753,20 +737,13 @@ VCG_API int vcg_cross_attn_kv_bwd(int dtype, const void* q, long long ldq, const
                                   float* d_ws, void* dq, long long lddq, void* dkv, long long lddkv,
                                   int B, int nh, int dh, int Lq, int Lk, float scale, float dropout_p,
                                   unsigned long long seed, hipStream_t s) {
-  VCG_REQUIRE(dh == DH, "head dim must be 64");
-  VCG_REQUIRE(q && kv && dctx && stats && d_ws && dq && dkv, "null argument");
-  VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
-  VCG_REQUIRE(B > 0 && nh > 0 && Lq >= 1 && Lk >= 1, "bad shape");
-  VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
-  const long long H = (long long)nh * DH;
-  VCG_REQUIRE(ldq >= H && lddo >= H && lddq >= H && ldkv >= 2 * H && lddkv >= 2 * H,
-              "a row pitch is below H (q, dctx, dq) or 2 H (kv, dkv)");
+  const int rc = cross_check(__func__, q && kv && dctx && stats && d_ws && dq && dkv, dtype, B, nh, dh, Lq, Lk,
+                             dropout_p, {{q, ldq, 1}, {kv, ldkv, 2}, {dctx, lddo, 1}, {dq, lddq, 1}, {dkv, lddkv, 2}},
+                             "a row pitch is below H (q, dctx, dq) or 2 H (kv, dkv)",
+                             (long long)B * nh * Lq < (1LL << 31) && (long long)B * nh * Lk < (1LL << 31));
+  if (rc != VCG_OK) return rc;
   const int nQ = (Lq + QT - 1) / QT, nK = (Lk + LT - 1) / LT;
-  VCG_REQUIRE((long long)B * nh * Lq < (1LL << 31) && (long long)B * nh * Lk < (1LL << 31), "grid too large");
   if (dtype == VCG_BF16) {
-    VCG_REQUIRE(ldq % 8 == 0 && ldkv % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0 && lddkv % 8 == 0 && aligned16(q) &&
-                    aligned16(kv) && aligned16(dctx) && aligned16(dq) && aligned16(dkv),
-                "16-B alignment");
     hipLaunchKernelGGL(cross_attn_kv_dq_kernel, dim3(B * nh * nQ), dim3(256), 0, s, (const bf16_t*)q, ldq,
                        (const bf16_t*)kv, ldkv, key_mask, (const bf16_t*)dctx, lddo, (const float2*)stats, d_ws,
                        (bf16_t*)dq, lddq, nh, Lq, Lk, nQ, scale, dropout_p, (uint64_t)seed);
@@ -787,41 +764,33 @@ VCG_API int vcg_cross_attn_kv_bwd(int dtype, const void* q, long long ldq, const
   return VCG_OK;
 }
 
-VCG_API int vcg_pegasus_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B,
-                                  int L, int H, int V, int n_pos, float scale, int pos0, hipStream_t s) {
-  VCG_REQUIRE(ids && tok && pos && out, "null argument");
-  VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
-  VCG_REQUIRE(B > 0 && L > 0 && H > 0 && V > 0 && n_pos > 0 && pos0 >= 0, "bad shape");
-  VCG_REQUIRE((long long)pos0 + L <= n_pos, "position pos0 + L - 1 is outside the position table");
-  VCG_REQUIRE((long long)B * L < (1LL << 31), "grid too large");
-  if (dtype == VCG_BF16)
-    hipLaunchKernelGGL(pegasus_embed_fwd_kernel<bf16_t>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (bf16_t*)out, L, H,
-                       V, scale, pos0);
-  else
-    hipLaunchKernelGGL(pegasus_embed_fwd_kernel<float>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (float*)out, L, H, V,
-                       scale, pos0);
-  VCG_LAUNCH_CHECK();
-  return VCG_OK;
-}
-
+// (p = 0 launches the DROP = false instantiation: the inference kernel)
 VCG_API int vcg_pegasus_embed_fwd_ex(int dtype, const long long* ids, const float* tok, const float* pos, void* out,
                                      int B, int L, int H, int V, int n_pos, float scale, int pos0, float dropout_p,
                                      unsigned long long seed, hipStream_t s) {
   VCG_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
-  if (dropout_p == 0.f) return vcg_pegasus_embed_fwd(dtype, ids, tok, pos, out, B, L, H, V, n_pos, scale, pos0, s);
   VCG_REQUIRE(ids && tok && pos && out, "null argument");
   VCG_REQUIRE(dtype == VCG_F32 || dtype == VCG_BF16, "dtype must be VCG_F32 or VCG_BF16");
   VCG_REQUIRE(B > 0 && L > 0 && H > 0 && V > 0 && n_pos > 0 && pos0 >= 0, "bad shape");
   VCG_REQUIRE((long long)pos0 + L <= n_pos, "position pos0 + L - 1 is outside the position table");
   VCG_REQUIRE((long long)B * L < (1LL << 31), "grid too large");
+  const bool drop = dropout_p > 0.f;
   if (dtype == VCG_BF16)
-    hipLaunchKernelGGL(pegasus_embed_drop_fwd_kernel<bf16_t>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (bf16_t*)out,
-                       L, H, V, scale, pos0, dropout_p, (uint64_t)seed);
+    hipLaunchKernelGGL((drop ? pegasus_embed_fwd_kernel<bf16_t, true> : pegasus_embed_fwd_kernel<bf16_t, false>),
+                       dim3(B * L), dim3(256), 0, s, ids, tok, pos, (bf16_t*)out, L, H, V, scale, pos0, dropout_p,
+                       (uint64_t)seed);
   else
-    hipLaunchKernelGGL(pegasus_embed_drop_fwd_kernel<float>, dim3(B * L), dim3(256), 0, s, ids, tok, pos, (float*)out, L,
-                       H, V, scale, pos0, dropout_p, (uint64_t)seed);
+    hipLaunchKernelGGL((drop ? pegasus_embed_fwd_kernel<float, true> : pegasus_embed_fwd_kernel<float, false>),
+                       dim3(B * L), dim3(256), 0, s, ids, tok, pos, (float*)out, L, H, V, scale, pos0, dropout_p,
+                       (uint64_t)seed);
   VCG_LAUNCH_CHECK();
   return VCG_OK;
+}
+
+// (the inference entry: the training entry without dropout, which holds the checks)
+VCG_API int vcg_pegasus_embed_fwd(int dtype, const long long* ids, const float* tok, const float* pos, void* out, int B,
+                                  int L, int H, int V, int n_pos, float scale, int pos0, hipStream_t s) {
+  return vcg_pegasus_embed_fwd_ex(dtype, ids, tok, pos, out, B, L, H, V, n_pos, scale, pos0, 0.f, 0, s);
 }
 
 // the four streaming kernels of the dropout sites: one thread per 8 elements; T in the argument list is the element
